@@ -21,9 +21,16 @@ fp32-equivalent, csrc/x3.h).  Since round 4 the 256x256 weight-gradient GEMMs us
 products, per-product error <= 3 * 2^-18; every parameter gradient at 3e-6 of the fp64 oracle, the whole GPU suite runs in both
 modes); the sub-record `wgrad_bf16x3` is the same step with the fp32-equivalent form there too -- `dtype` says which.
 
-Timing: W warm-up steps, then --windows windows of EXACTLY K steps each, every window bracketed by a barrier + device
-synchronisation on both sides and reduced with MAX over the ranks (sub-records: --sub-windows windows each, median).  `ms_per_step` / `value` are the MEDIAN window (the chip's DVFS and
-the boxes of the pool move a 20-step window by 1-2 %); `windows_ms_per_step` lists them all, `ms_per_step_min` is the fastest.
+Timing: W warm-up steps, then --windows windows (default 1, so that the headline times exactly K steps) of EXACTLY K steps each, every
+window bracketed by a barrier + device synchronisation on both sides and reduced with MAX over the ranks (sub-records: --sub-windows windows
+each, median).  On one GPU `ms_per_step` / `value` are the MEDIAN timed step, read off HIP events recorded between the steps on the
+caller's stream (a one-off stall moves one step, not the figure); with N ranks they are the MEDIAN window, max over the ranks (the
+chip's DVFS and the boxes of the pool move a 20-step window by 1-2 %).  `windows_ms_per_step` lists the windows' wall times per step,
+`ms_per_step_min` is the fastest.
+
+--dump-outputs DIR: what the last timed headline step computed -- the render outputs, the loss terms, and after the optimizer step every
+parameter gradient and parameter -- as DIR/<name>.npy (float32), at most 64 MB in all.  Weights (torch.manual_seed(0)), rays and ground
+truth (seeded generators) are the same in every run with the same arguments, so two builds can be compared output for output.
 
 Per-entry-point times (`kernels`, `roofline`): the timed steps run the per-point entry points as a CHAIN of point ranges on several
 streams (include/i2sdf.h: I2SDF_OPT_PARTS), where an entry point has no duration of its own.  They are therefore measured live in
@@ -63,8 +70,12 @@ def parse():
     ap.add_argument("--scaling", default="both", choices=["weak", "strong", "both"],
                     help="which scaling mode(s) to time; `value`/`scaling` of the JSON line are the weak ones unless --scaling strong")
     ap.add_argument("--sampler-iters", type=int, default=2, help="fixed sampler iterations k (0 = data dependent)")
-    ap.add_argument("--windows", type=int, default=7, help="timed windows of --steps steps each (median reported)")
+    ap.add_argument("--windows", type=int, default=1, help="timed windows of --steps steps each (median reported); the default, one window, "
+                                                           "makes --steps the number of timed steps of the headline")
     ap.add_argument("--sub-windows", type=int, default=3, help="timed windows of every sub-record (strong, dense128, k1, k5, natural_k, wgrad_bf16x3, rays4096, cfg3)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed headline step computed (render outputs, loss terms, parameter gradients, updated "
+                         "parameters) as DIR/<name>.npy, float32, at most 64 MB in all (larger arrays as a fixed sample)")
     ap.add_argument("--profile-steps", type=int, default=10, help="steps of the per-entry-point timing pass behind the timed windows")
     ap.add_argument("--no-live-traffic", action="store_true", help="do not start the rocprofv3 --pmc passes for roofline.traffic / kernels_hbm")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)      # the run under rocprofv3: headline steps only, no output
@@ -193,10 +204,11 @@ class Workload:
             self.torch.distributed.barrier()
         self.torch.cuda.synchronize()
 
-    def run(self, B, seed, k_iters, steps, warmup, dense=0, timing=False, windows=1, profile_steps=0, no_sync=False):
+    def run(self, B, seed, k_iters, steps, warmup, dense=0, timing=False, windows=1, profile_steps=0, no_sync=False, keep_last=False):
         """-> dict(dt = median over `windows` windows of the seconds for `steps` steps (each max over ranks), dts, loss, iters, ktimes).
         dense > 0: `dense` uniform samples per ray, sampler bypassed (the dense-128 convention).
-        no_sync: the same steps with the gradient all-reduce suspended (i2sdf_amd.dist.no_sync) -- what the collective costs a step."""
+        no_sync: the same steps with the gradient all-reduce suspended (i2sdf_amd.dist.no_sync) -- what the collective costs a step.
+        keep_last: also return `last`, host copies of what the last timed step handed its caller (see last_step_arrays)."""
         torch, net = self.torch, self.net
         import contextlib
         from i2sdf_amd import dist as i2dist
@@ -209,8 +221,9 @@ class Workload:
             c, d, nrm = eng.ray_setup(inp["uv"], inp["pose"], inp["intrinsics"])
             z = torch.linspace(0.0, 6.0, dense + 1, device=self.dev).repeat(B, 1).contiguous()      # n samples + z_max column
             zs = (c, d, nrm, z, z[:, dense // 2:dense // 2 + 1].contiguous())
+        kept = {}
 
-        def step():
+        def step(keep=False):
             with sync_ctx():
                 out = net.render(inp, *zs) if zs else net(inp)
                 losses = self.loss_fn(out, gt, self.step_no)
@@ -218,19 +231,31 @@ class Workload:
                 losses["loss"].backward()
             self.opt.step()
             self.step_no += 1
+            if keep:
+                kept["out"], kept["losses"] = out, losses
             return losses["loss"]
 
         for _ in range(max(warmup, 1)):
             step()
         eng = net._engine_for(self.dev)
         dts = []
-        for _ in range(max(windows, 1)):                       # every window: exactly `steps` steps, barrier + synchronize on both sides
+        n_win = max(windows, 1)
+        # one GPU: an event on the caller's stream behind every timed step, so that a step's time can be read off the device timeline
+        # (the median step of the headline shrugs off a one-off stall that would move a single window's wall time)
+        evs = [[torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)] for _ in range(n_win)] if (timing and self.world == 1 and self.dev.type == "cuda") else None
+        for w in range(n_win):                                 # every window: exactly `steps` steps, barrier + synchronize on both sides
             self.fence()
             t0 = time.perf_counter()
-            for _ in range(steps):
-                loss = step()
+            if evs:
+                evs[w][0].record()
+            for s in range(steps):
+                loss = step(keep_last and w == n_win - 1 and s == steps - 1)
+                if evs:
+                    evs[w][s + 1].record()
             self.fence()
             dts.append(time.perf_counter() - t0)
+        step_ms = sorted(a.elapsed_time(b) for e in evs for a, b in zip(e[:-1], e[1:])) if evs else None
+        last = self.last_step_arrays(kept["out"], kept["losses"]) if kept else None
         t = torch.tensor(dts, dtype=torch.float64, device=self.dev)
         dts_min = None
         if self.world > 1:
@@ -253,7 +278,53 @@ class Workload:
             eng.use_chain = True
         med = sorted(dts)[len(dts) // 2]
         return {"dt": med, "dts": dts, "dts_rank_min": dts_min, "loss": float(loss.item()), "iters": int(net.last_sampler_iters.item()) if not dense else 0,
-                "ktimes": ktimes, "prof_steps": prof_steps, "eng": eng}
+                "ktimes": ktimes, "prof_steps": prof_steps, "eng": eng, "last": last, "step_ms": step_ms}
+
+    def last_step_arrays(self, out, losses):
+        """name -> host float array of what one training step hands its caller: the render outputs (out.*), the loss terms (loss.*),
+        and after the optimizer step every parameter gradient (grad.*) and updated parameter (param.*)."""
+        torch = self.torch
+
+        def host(x):
+            return x.detach().float().cpu().numpy()
+        arrs = {}
+        for k, v in out.items():
+            if torch.is_tensor(v):
+                arrs["out." + k] = host(v)
+        for k, v in losses.items():
+            if torch.is_tensor(v):
+                arrs["loss." + k] = host(v)
+        for n, p in self.net.named_parameters():
+            if p.grad is not None:
+                arrs["grad." + n] = host(p.grad)
+            arrs["param." + n] = host(p)
+        return arrs
+
+
+DUMP_LIMIT = 64 * 2 ** 20          # bytes, all --dump-outputs files together
+
+
+def dump_outputs(arrs, path, limit=DUMP_LIMIT):
+    """--dump-outputs: one DIR/<name>.npy per array.  If they exceed `limit` together, every array larger than an equal share of
+    what the whole ones leave is replaced by a fixed sample of its flattened elements (seeded by the array's name: the same
+    positions in every run with the same arguments)."""
+    import zlib
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    sizes = sorted((a.nbytes, k) for k, a in arrs.items())
+    left = share = limit - 256 * len(arrs)          # (room for the .npy headers)
+    for i, (nb, k) in enumerate(sizes):            # smallest first: the share of the remaining ones only grows
+        share = left // (len(sizes) - i)
+        if nb > share:
+            break
+        left -= nb
+    for k, a in arrs.items():
+        a = np.ascontiguousarray(a)
+        if a.nbytes > share:
+            m = max(share // a.itemsize, 1)
+            idx = np.random.default_rng(zlib.crc32(k.encode())).choice(a.size, size=m, replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 class _MockEngine:
@@ -315,9 +386,10 @@ class MockWorkload(Workload):
         if self.world > 1:
             self.torch.distributed.barrier()
 
-    def run(self, B, seed, k_iters, steps, warmup, dense=0, timing=False, windows=1, profile_steps=0, no_sync=False):
+    def run(self, B, seed, k_iters, steps, warmup, dense=0, timing=False, windows=1, profile_steps=0, no_sync=False, keep_last=False):
         self.args_dense = dense
-        return Workload.run(self, min(B, 64), seed, k_iters, steps, warmup, dense=0, timing=timing, windows=windows, profile_steps=0, no_sync=no_sync)
+        return Workload.run(self, min(B, 64), seed, k_iters, steps, warmup, dense=0, timing=timing, windows=windows, profile_steps=0, no_sync=no_sync,
+                            keep_last=keep_last)
 
 
 def main():
@@ -370,17 +442,22 @@ def main():
     # ---- headline: weak scaling, every rank draws its own `rays` rays -----------------------------------------------
     SW = max(args.sub_windows, 1)
     weak = strong = None
+    dump = args.dump_outputs is not None and rank == 0
     if args.scaling in ("weak", "both"):
         weak = wl.run(B, 1000 + rank, args.sampler_iters, K, W, timing=True, windows=args.windows,
-                      profile_steps=args.profile_steps)      # each rank draws its own rays (ray-sharded data parallelism)
+                      profile_steps=args.profile_steps, keep_last=dump)      # each rank draws its own rays (ray-sharded data parallelism)
     if args.scaling in ("strong", "both"):
         Bs = args.strong_rays // world                    # fixed GLOBAL batch, split over the ranks
         strong = wl.run(Bs, 2000 + rank, args.sampler_iters, K, W, timing=(weak is None), windows=(args.windows if weak is None else SW),
-                        profile_steps=(args.profile_steps if weak is None else 0))
+                        profile_steps=(args.profile_steps if weak is None else 0), keep_last=(dump and weak is None))
         strong["rays_per_gpu"] = Bs
     head = weak if weak is not None else strong
+    if dump:
+        dump_outputs(head.pop("last"), args.dump_outputs)
     head_B = B if weak is not None else strong["rays_per_gpu"]
     dt, iters, ktimes = head["dt"], head["iters"], head["ktimes"]
+    if head["step_ms"]:             # one GPU: the median timed step on the device timeline (HIP events between the steps)
+        dt = head["step_ms"][len(head["step_ms"]) // 2] * 1e-3 * K
     ms = dt / K * 1e3
     value = head_B * n_shaded * world / (dt / K)
 
@@ -542,7 +619,9 @@ def main():
             "metric": "ray-samples/sec (fwd+bwd)", "value": round(value, 1), "unit": "ray-samples/s", "n_gpus": world, "steps": K,
             "warmup": W, "ms_per_step": round(ms, 4), "higher_is_better": True, "scaling": "weak" if weak is not None else "strong",
             "windows_ms_per_step": [round(x / K * 1e3, 4) for x in head["dts"]], "ms_per_step_min": round(min(head["dts"]) / K * 1e3, 4),
-            "timing": f"median of {len(head['dts'])} windows of exactly {K} steps each (barrier + synchronize around every window, max over ranks)",
+            "timing": (f"{len(head['dts'])} window(s) of exactly {K} steps each (barrier + synchronize around every window); ms_per_step: the median "
+                       f"of the {len(head['step_ms'])} timed steps, HIP events between the steps" if head["step_ms"] else
+                       f"median of {len(head['dts'])} windows of exactly {K} steps each (barrier + synchronize around every window, max over ranks)"),
             "vs_baseline": None,
             "dtype": "f32" if not any_x3 else ("f32 (bf16x3 split MFMA: fp32 operands as 3 bf16 terms, fp32 accumulate"
                                                 + ("; the 256x256 weight-gradient GEMM blocks" + (" and the sampler's depth-choosing sdf-only passes" if getattr(eng, "sampler_bf16x2", False) else "")

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Generate the committed golden vectors (tests/golden/*.npz) by RUNNING THE REFERENCE in this container.
 
-    python tests/golden/gen_golden.py          # needs /root/reference; writes tests/golden/g*.npz
+    python tests/golden/gen_golden.py          # needs /root/reference; writes tests/golden/g*.npz (+ g17_configs.json)
+    python tests/golden/gen_golden.py vsref    # G17 only
 
 The reference (pure Python/PyTorch) is imported through tests/golden/ref_import.py with stub modules for its
 off-path dependencies.  Only data (inputs, parameters of tiny networks, expected outputs) is written; no
@@ -211,6 +212,101 @@ def full_width(ref_model, I2SDFLoss):
     save("g15_eval_full", **arrs)
 
 
+def vs_reference_fixtures():
+    """G17 (tests/test_oracle_vs_reference.py, tests/test_host_logic.py): the reference's two shipped configs and its full-size
+    networks.  g17_configs.json holds the parsed `model:` / `loss:` nodes of config/synthetic.yml and synthetic_light_mask.yml.
+    g17_full_size.npz holds, per config, the state_dict shapes and the init structure of the reference's own initialisation
+    (torch.manual_seed(0)), then -- on weights both sides rebuild with oracle.init_params(seed) (checksummed, as G14) -- the
+    reference's eval forward of 24 rays, and one training step of 16 rays with every random draw it made, its outputs, loss and
+    parameter gradients (small tensors whole, large ones as max |g| and seeded Gaussian projections)."""
+    import json
+    sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+    from oracle import i2sdf_oracle as orc
+    from helpers import camera_inputs, gaussian_projections, make_gt
+    ref_model, _ = ref_import.import_reference()
+    from model.network import I2SDFLoss
+    ymls = {"synthetic.yml": False, "synthetic_light_mask.yml": True}
+    confs = {}
+    for yml in ymls:
+        c = ref_import.load_cfg(yml)
+        confs[yml] = {"model": c["model"], "loss": c["loss"]}
+    path = os.path.join(HERE, "g17_configs.json")
+    with open(path, "w") as f:
+        json.dump(confs, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print(f"wrote {path}")
+    arrs = {}
+
+    def build(yml, seed):
+        conf = ref_import.load_cfg(yml)
+        conf.model.use_normal = True
+        torch.manual_seed(0)
+        net = ref_model.I2SDFNetwork(conf.model)
+        if seed is not None:
+            sd = orc.init_params(orc.NetCfg.from_conf(conf.model), seed=seed)
+            sd["density.beta"] = net.state_dict()["density.beta"].clone()
+            net.load_state_dict(sd)
+        return net, conf
+
+    for yml, light in ymls.items():
+        tag = "light." if light else "plain."
+        net, _ = build(yml, None)
+        for k, v in net.state_dict().items():
+            arrs[tag + "init_shape." + k] = np.array(v.shape, dtype=np.int64)
+        if not light:
+            arrs[tag + "init.lin8_weight_v_mean"] = net.state_dict()["implicit_network.lin8.weight_v"].double().mean()
+            arrs[tag + "init.lin8_bias"] = net.state_dict()["implicit_network.lin8.bias"]
+    # eval forward, full size (the parametrisation of test_eval_forward_full_size)
+    for yml, light, t, beta, seed in (("synthetic.yml", False, (0.1, -0.2, 0.3), 0.1, 171), ("synthetic_light_mask.yml", True, (0.0, 0.0, -2.0), 0.02, 172)):
+        tag = "eval_" + ("light." if light else "plain.")
+        net, _ = build(yml, seed)
+        net.eval()
+        with torch.no_grad():
+            net.density.beta.fill_(beta)
+        inp = camera_inputs(24, t, train_layout=False)
+        with torch.no_grad():
+            out = net(inp)
+        arrs.update({tag + "in." + k: v for k, v in inp.items()})
+        arrs.update({tag + "out." + k: v for k, v in out.items()})
+        arrs[tag + "init_seed"], arrs[tag + "beta"] = np.int64(seed), np.float32(beta)
+        arrs[tag + "sd_checksum"] = torch.stack([v.double().sum() for k, v in net.state_dict().items() if k != "density.beta"])
+    # one training step, full size, with the draws the reference made (test_train_step_full_size_with_captured_draws)
+    net, conf = build("synthetic.yml", 173)
+    net.train()
+    with torch.no_grad():
+        net.density.beta.fill_(0.05)
+    B = 16
+    inp = camera_inputs(B, (0.0, 0.0, -2.0), seed=2)
+    gt = make_gt(B)
+    np.random.seed(0)
+    with DrawRecorder() as rec:
+        out = net(inp)
+    losses = I2SDFLoss(**conf.loss)(out, gt, 10)
+    net.zero_grad()
+    losses["loss"].backward()
+    tag = "train."
+    arrs.update({tag + "in." + k: v for k, v in inp.items()})
+    arrs.update({tag + "gt." + k: v for k, v in gt.items()})
+    arrs.update({tag + "out." + k: v for k, v in out.items()})
+    arrs.update({tag + "loss." + k: v for k, v in losses.items()})
+    # gradients: tensors of <= 1024 elements whole; of every larger one its shape, max |g| and N_PROJ seeded Gaussian projections
+    # (helpers.gaussian_projections), from which the test bounds the 2-norm -- hence the max norm -- of its difference to these
+    for n, p in net.named_parameters():
+        if p.grad is None:
+            continue
+        if p.grad.numel() <= 1024:
+            arrs[tag + "grad." + n] = p.grad
+        else:
+            arrs[tag + "gshape." + n] = np.array(p.grad.shape, dtype=np.int64)
+            arrs[tag + "gmax." + n] = p.grad.double().abs().max()
+            arrs[tag + "gproj." + n] = gaussian_projections(p.grad, n)
+    for key, i in (("strat_u", 0), ("cdf_u", 1), ("extra_idx", 2), ("eik_idx", 3), ("eik_pts", 4), ("nbr_off", 5)):
+        arrs[tag + "draw." + key] = rec.log[i][1][:32] if key == "extra_idx" else rec.log[i][1]
+    arrs[tag + "init_seed"] = np.int64(173)
+    arrs[tag + "sd_checksum"] = torch.stack([v.double().sum() for k, v in net.state_dict().items() if k != "density.beta"])
+    save("g17_full_size", **arrs)
+
+
 def n4_fixtures():
     """G16: the reference's marching-cubes grids (utils/plots.py get_grid_uniform / get_grid) and its bubble-PDF update
     (ReconstructionTrainer.update_pdf, model/trainer/recon.py:142-152, fed as in :195-199)."""
@@ -263,6 +359,8 @@ def n4_fixtures():
 def main():
     if sys.argv[1:] == ["n4"]:
         return n4_fixtures()
+    if sys.argv[1:] == ["vsref"]:
+        return vs_reference_fixtures()
     ref_model, ref_utils = ref_import.import_reference()
     from model.network.embedder import get_embedder
     from model.network.mlp import ImplicitNetwork, RenderingNetwork
@@ -492,6 +590,9 @@ def main():
 
     # ---- G16 marching-cubes grids + bubble-PDF update ---------------------------------
     n4_fixtures()
+
+    # ---- G17 the shipped configs and the full-size networks (tests/test_oracle_vs_reference.py) ------
+    vs_reference_fixtures()
 
 
 if __name__ == "__main__":

@@ -245,3 +245,15 @@ def memo(key, fn):
     if key not in _MEMO:
         _MEMO[key] = fn()
     return _MEMO[key]
+
+
+N_PROJ = 256
+
+
+def gaussian_projections(x, name, k=N_PROJ, chunk=32):
+    """k inner products of the flattened tensor x with fixed standard-normal vectors (numpy PCG64, seeded by `name`), float64.
+    For an error vector e, mean((R e)^2) estimates |e|_2^2: what a fixture stores in place of a tensor too large to keep whole."""
+    import zlib
+    x = torch.as_tensor(x).detach().cpu().double().reshape(-1).numpy()
+    rng = np.random.default_rng(zlib.crc32(name.encode()))
+    return np.concatenate([rng.standard_normal((min(chunk, k - i), x.size)) @ x for i in range(0, k, chunk)])
