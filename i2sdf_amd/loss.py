@@ -5,8 +5,49 @@ SURVEY row N1); the masked means are sums over selected rows / number of selecte
 indexing (`depth[depth_mask]`, :320-329) computes, without its device->host synchronisation."""
 from __future__ import annotations
 
+import weakref
+
 import torch
 import torch.nn as nn
+
+# the outputs of a training render that the fused path (i2sdf_render_loss_backward) reads and seeds
+FUSED_OUTPUT_KEYS = ("rgb_values", "depth_values", "weight_sum", "normal_values", "grad_theta", "diff_norm", "surface_sdf", "light_mask")
+
+
+def record_outputs(out):
+    """What the fused path later checks the outputs of a training render against: per output a weak reference to the tensor and to its
+    grad_fn (no reference cycle through the render's state, which holds this record), its version counter and its shape."""
+    return {k: (weakref.ref(v), None if v.grad_fn is None else weakref.ref(v.grad_fn), v._version, tuple(v.shape))
+            for k, v in out.items() if k in FUSED_OUTPUT_KEYS}
+
+
+def fast_path_refusal(rec, out):
+    """None if the fused path may hand its unscaled placeholder seeds to autograd for these outputs, else the reason it may not.
+
+    `out` must hold exactly the recorded tensors (the same objects: a detach / clone / slice / view of one shares storage but is another
+    tensor), each unchanged since the render (version counter, shape, grad_fn) and with nothing that observes or edits the gradient
+    arriving at it (a tensor hook, retain_grad()).  Anything else must see real gradients: the render's backward then takes its general
+    path.  Pure host logic (tests/test_host_logic.py)."""
+    if rec is None:
+        return "no record of the render's outputs"
+    for k in FUSED_OUTPUT_KEYS:
+        if (k in out) != (k in rec):
+            return f"{k}: {'added to' if k in out else 'missing from'} the render's outputs"
+    for k, (ref, fn_ref, version, shape) in rec.items():
+        t = out[k]
+        if ref() is not t:
+            return f"{k}: not the tensor the render returned"
+        if t.grad_fn is None or fn_ref is None or fn_ref() is not t.grad_fn:
+            return f"{k}: grad_fn changed or missing"
+        if t._version != version:
+            return f"{k}: modified in place"
+        if tuple(t.shape) != shape:
+            return f"{k}: shape changed"
+        if t._backward_hooks:
+            return f"{k}: has a tensor hook"
+        if t.retains_grad:
+            return f"{k}: retains its gradient"
+    return None
 
 
 class _FusedLossFn(torch.autograd.Function):
@@ -63,10 +104,12 @@ class _FusedRenderLossFn(torch.autograd.Function):
     scaling (1), the eikonal outputs' backward, the seeds, the compositing backward and the beta reduction (4 + 1).  The per-output
     gradients are handed to autograd UNSCALED as recognisable placeholders: _RenderFn.backward checks that they arrive untouched (nobody
     else differentiated the same outputs), multiplies the prepared per-sample gradients by the upstream gradient in one launch and
-    continues with the radiance backward; if they were mixed with other gradients it corrects them and takes the general path."""
+    continues with the radiance backward; if they were mixed with other gradients it corrects them and takes the general path.  That
+    correction is exact only for ADDED gradients: backward re-checks the outputs (fast_path_refusal: a hook, retain_grad() or an in-place
+    edit since the loss) and hands autograd real, scaled seeds whenever placeholders could be observed or transformed on their way."""
 
     @staticmethod
-    def forward(ctx, cfg, n_pc, gt, h, rgb, depth, wsum, normal, grad_theta, diff_norm, surface, lmask):
+    def forward(ctx, cfg, n_pc, gt, h, outs, rgb, depth, wsum, normal, grad_theta, diff_norm, surface, lmask):
         from . import lib as L
         lib = L.load()
         fz = h["fused"]
@@ -107,8 +150,10 @@ class _FusedRenderLossFn(torch.autograd.Function):
         if diff_norm is not None and not (cfg._obj.smooth_on and cfg._obj.smooth_w > 0):
             toks[5] = None      # smoothness term inactive: no gradient for diff_norm (as in _FusedLossFn)
             pre["tok"]["diff_norm"] = None
+        # seeds that are identically zero for this loss configuration: the only outputs whose gradient may arrive as None on the fast path
+        pre["zero"] = {"wsum": gts[5] is None, "lmask": gts[6] is None}
         h["pre"] = pre
-        ctx.pre, ctx.toks, ctx.h = pre, toks, h
+        ctx.pre, ctx.toks, ctx.h, ctx.outs = pre, toks, h, outs      # (outs: the render's outputs, strong references until backward)
         ctx.mark_non_differentiable(losses)
         ctx.set_materialize_grads(False)
         return total, losses
@@ -116,17 +161,18 @@ class _FusedRenderLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g, _g_items):
         if g is None:
-            return (None,) * (4 + len(ctx.toks))
-        pre, toks, h = ctx.pre, ctx.toks, ctx.h
-        ctx.pre = ctx.toks = ctx.h = None
-        if h.get("pre") is not pre:
-            # a later loss call on the same outputs replaced this call's prepared gradients (or the render's backward already ran): the
-            # placeholders mean nothing to _RenderFn.backward any more -- hand autograd the real thing, seeds times the upstream gradient
+            return (None,) * (5 + len(ctx.toks))
+        pre, toks, h, outs = ctx.pre, ctx.toks, ctx.h, ctx.outs
+        ctx.pre = ctx.toks = ctx.h = ctx.outs = None
+        if h.get("pre") is not pre or fast_path_refusal(h.get("out_rec"), outs) is not None:
+            # a later loss call on the same outputs replaced this call's prepared gradients (or the render's backward already ran), or
+            # something between here and the render observes or transforms the outputs' gradients (a hook, retain_grad(), an in-place edit
+            # after the loss): hand autograd the real thing, seeds times the upstream gradient; _RenderFn.backward takes its general path
             live = [t for t in toks if t is not None]
             scaled = iter(torch._foreach_mul(live, g))
-            return (None, None, None, None) + tuple((next(scaled) if t is not None else None) for t in toks)
+            return (None,) * 5 + tuple((next(scaled) if t is not None else None) for t in toks)
         pre["g"] = g
-        return (None, None, None, None) + tuple(toks)
+        return (None,) * 5 + tuple(toks)
 
 
 class I2SDFLoss(nn.Module):
@@ -182,7 +228,8 @@ class I2SDFLoss(nn.Module):
                  "light_mask_loss"]
         h = self._render_handle(out, cfg)
         if h is not None:
-            total, vec = _FusedRenderLossFn.apply(C.byref(cfg), 0 if surf is None else surf.shape[0], gtc, h, *args)
+            outs = {k: out[k] for k in FUSED_OUTPUT_KEYS if k in out}
+            total, vec = _FusedRenderLossFn.apply(C.byref(cfg), 0 if surf is None else surf.shape[0], gtc, h, outs, *args)
             res = {n: vec[i] for i, n in enumerate(names)}
             res["loss"] = total
             return res
@@ -201,7 +248,7 @@ class I2SDFLoss(nn.Module):
 
     @staticmethod
     def _render_handle(out, cfg):
-        """The state of the training render these outputs came from, if they ARE its outputs (same tensors, graph attached, grad mode on)
+        """The state of the training render these outputs came from, if they ARE its outputs, untouched (fast_path_refusal), grad mode is on
         and nothing needs the separate path (data-parallel exchange of the loss denominators; I2SDF_FUSED_RENDER_LOSS=0 for A/B runs)."""
         import os
         rgb = out["rgb_values"]
@@ -210,10 +257,8 @@ class I2SDFLoss(nn.Module):
             return None
         if os.environ.get("I2SDF_FUSED_RENDER_LOSS", "1") == "0":
             return None
-        ptrs = h.get("out_ptrs", {})
-        for k in ("rgb_values", "depth_values", "weight_sum", "normal_values", "grad_theta", "diff_norm", "surface_sdf", "light_mask"):
-            if (k in out) != (k in ptrs) or (k in out and (out[k].data_ptr() != ptrs[k] or not out[k].is_contiguous())):
-                return None
+        if fast_path_refusal(h.get("out_rec"), out) is not None:
+            return None
         if ("grad_theta" in out) != ("diff_norm" in out) or out["rgb_values"].dtype != torch.float32:
             return None
         return h

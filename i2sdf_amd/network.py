@@ -154,9 +154,11 @@ class _RenderFn(torch.autograd.Function):
         same = lambda a, b: a is not None and b is not None and a.data_ptr() == b.data_ptr() and a.numel() == b.numel()
         if pre is not None and pre["g"] is not None:
             tk = pre["tok"]
-            fast = (same(g_rgb, tk["rgb"]) and same(g_depth, tk["depth"]) and (g_wsum is None or same(g_wsum, tk["wsum"]))
+            # a gradient may be missing only where the loss's seed is identically zero (a detached weight_sum under a mask term is not)
+            fast = (same(g_rgb, tk["rgb"]) and same(g_depth, tk["depth"])
+                    and ((g_wsum is None and pre["zero"]["wsum"]) or same(g_wsum, tk["wsum"]))
                     and ((not st["want_normal"]) or tk["normal"] is None or same(g_normal, tk["normal"]))
-                    and ((not net.use_light) or same(g_lmask, tk["lmask"]))
+                    and ((not net.use_light) or (g_lmask is None and pre["zero"]["lmask"]) or same(g_lmask, tk["lmask"]))
                     and ((not n_eik) or same(g_eik, pre["tok_eik"]))
                     and ((not n_pc) or tk["surface"] is None or same(g_surf, tk["surface"])))
             if fast:
@@ -172,7 +174,7 @@ class _RenderFn(torch.autograd.Function):
             if n_eik and g_eik is not None and not same(g_eik, pre["tok_eik"]):
                 pass      # (_EikonalOutputsFn.backward applied the same correction to grad_theta / diff_norm before its own backward)
             elif n_eik and same(g_eik, pre["tok_eik"]):
-                g_eik = pre["eik_true"]()          # the placeholder reached us: recompute the extra points' gradient the general way
+                g_eik = pre["eik_true"](pre["g"])  # the placeholder reached us: recompute the extra points' gradient the general way
         sbar = torch.empty(M_sdf, device=dev)
         nbar = torch.empty(M_sdf, 3, device=dev)
         if g_rgb is None:                      # a loss without a colour term: the compositing backward wants the pointer
@@ -214,7 +216,9 @@ class _RenderFn(torch.autograd.Function):
                 cnt *= s
             grads.append(gflat[off:off + cnt].view(shape))
         st.pop("fused", None)
-        st.pop("pre", None)
+        pre = st.pop("pre", None)
+        if pre is not None:
+            pre.clear()          # its seeds and eik_true's captures go now, not at the next cyclic collection
         ctx.net = ctx.st = ctx.fw = ctx.comp = None
         return (None, None) + tuple(grads)
 
@@ -283,8 +287,9 @@ class _EikonalOutputsFn(torch.autograd.Function):
                 # the fused loss's own seeds, untouched: the extra points' gradient rows were already written by i2sdf_render_loss_backward;
                 # hand the placeholder on, so that _RenderFn.backward can tell that nobody else contributed.  `eik_true` computes the real
                 # thing if the placeholder should meet other gradients further down after all.
-                g_th, g_df, ga = g_theta, g_diff, g_all
-                pre["eik_true"] = lambda: _EikonalOutputsFn._bwd(ga, g_th * pre["g"].reshape(()), None if g_df is None else g_df * pre["g"].reshape(()), ctx.B)
+                # (captures neither `pre` nor ctx: no reference cycle through the render's state)
+                g_th, g_df, ga, B = g_theta, g_diff, g_all, ctx.B
+                pre["eik_true"] = lambda g: _EikonalOutputsFn._bwd(ga, g_th * g.reshape(()), None if g_df is None else g_df * g.reshape(()), B)
                 return pre["tok_eik"], None, None
             gs_ = pre["g"].reshape(()).to(torch.float32) - 1.0          # unscaled seeds mixed with other gradients: g * seed + the rest
             if g_theta is not None and tk["grad_theta"] is not None:
@@ -502,9 +507,11 @@ class I2SDFNetwork(nn.Module):
                 self._eikonal_outputs(out, g_eik, surf, N, n_pc, st)
                 if self.use_normal:
                     out["normal_values"] = normal
-                # I2SDFLoss looks for this handle: with it, loss + render backward run as one fused library call (loss.py).  The pointers
-                # identify the outputs (a clone / detach / slice of one is a different tensor: the loss then takes its general path)
-                st["out_ptrs"] = {k: v.data_ptr() for k, v in out.items()}
+                # I2SDFLoss looks for this handle: with it, loss + render backward run as one fused library call (loss.py).  The record
+                # identifies the outputs by object (a clone / detach / slice of one is a different tensor, an in-place edit bumps its
+                # version: the loss then takes its general path -- loss.fast_path_refusal)
+                from .loss import record_outputs
+                st["out_rec"] = record_outputs(out)
                 rgb._i2sdf_render = st
             else:
                 out["normal_map"] = normal.detach()

@@ -139,3 +139,88 @@ def test_knockout_patches_match_the_current_sources():
         for fn, old, new in patches:
             assert open(os.path.join(m.CSRC, fn)).read().count(old) == 1, (name, fn)
     assert "I2SDF_ABL" not in open(os.path.join(m.CSRC, "common.h")).read()
+
+
+# ---- the fused render+loss path's identity check (i2sdf_amd.loss.fast_path_refusal): which outputs may receive placeholder seeds --------
+class _StubRender(torch.autograd.Function):
+    """CPU stand-in for the training render: several differentiable outputs from one node, as _RenderFn / _EikonalOutputsFn produce."""
+
+    @staticmethod
+    def forward(ctx, x):
+        return x[:, :3] * 2, x[:, 3] * 3, x[:, 4:5] * 0.5
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_depth, g_wsum):
+        raise AssertionError("not differentiated here")
+
+
+def _no_grad(fn):
+    with torch.no_grad():
+        fn()
+
+
+def _stub_outputs(B=5):
+    from i2sdf_amd.loss import record_outputs
+    x = torch.rand(B, 5, requires_grad=True)
+    rgb, depth, wsum = _StubRender.apply(x)
+    out = {"rgb_values": rgb, "depth_values": depth, "weight_sum": wsum}
+    return out, record_outputs(out)
+
+
+def test_fast_path_accepts_the_untouched_outputs():
+    from i2sdf_amd.loss import fast_path_refusal
+    out, rec = _stub_outputs()
+    assert fast_path_refusal(rec, out) is None
+    assert fast_path_refusal(rec, dict(out)) is None                       # another dict holding the same tensors
+    # an extra key the fused path does not read is no reason to refuse; a missing record is
+    assert fast_path_refusal(rec, dict(out, other=torch.zeros(1))) is None
+    assert fast_path_refusal(None, out) is not None
+    # the record holds no strong reference: it does not keep the outputs alive
+    import gc
+    import weakref
+    r = weakref.ref(out["depth_values"])
+    del out
+    gc.collect()
+    assert r() is None
+
+
+@pytest.mark.parametrize("edit,reason", [
+    (lambda o: o.__setitem__("weight_sum", o["weight_sum"].detach()), "not the tensor"),                 # shares storage and data_ptr
+    (lambda o: o.__setitem__("depth_values", o["depth_values"].detach().requires_grad_()), "not the tensor"),
+    (lambda o: o.__setitem__("depth_values", o["depth_values"][:3]), "not the tensor"),                  # leading slice: same data_ptr, contiguous
+    (lambda o: o.__setitem__("rgb_values", o["rgb_values"].view(-1, 3)), "not the tensor"),              # a view of the same shape
+    (lambda o: o.__setitem__("rgb_values", o["rgb_values"].clone()), "not the tensor"),
+    (lambda o: o.pop("weight_sum"), "missing"),
+    (lambda o: o.__setitem__("normal_values", torch.zeros(5, 3)), "added"),
+    (lambda o: o["depth_values"].register_hook(lambda g: g.clamp(-1e-3, 1e-3)), "hook"),
+    (lambda o: o["depth_values"].register_hook(lambda g: g.mul_(0.5)), "hook"),
+    (lambda o: o["rgb_values"].retain_grad(), "retains"),
+    (lambda o: o["depth_values"].clamp_(0.0, 1.0), "grad_fn"),                                            # grad_fn and version change
+    (lambda o: _no_grad(lambda: o["weight_sum"].mul_(2.0)), "in place"),                                  # version changes, grad_fn does not
+])
+def test_fast_path_refuses(edit, reason):
+    from i2sdf_amd.loss import fast_path_refusal
+    out, rec = _stub_outputs()
+    edit(out)
+    why = fast_path_refusal(rec, out)
+    assert why is not None and reason in why, why
+
+
+def test_fast_path_refuses_a_changed_shape_or_a_missing_grad_fn():
+    """The two checks no public operation reaches without also changing identity, grad_fn or version: exercised on the record."""
+    from i2sdf_amd.loss import fast_path_refusal
+    out, rec = _stub_outputs()
+    ref, fn_ref, version, shape = rec["depth_values"]
+    rec_shape = dict(rec, depth_values=(ref, fn_ref, version, (shape[0] + 1,)))
+    assert "shape" in fast_path_refusal(rec_shape, out)
+    rec_fn = dict(rec, depth_values=(ref, None, version, shape))
+    assert "grad_fn" in fast_path_refusal(rec_fn, out)
+    leaf = torch.rand(5, requires_grad=True)
+    from i2sdf_amd.loss import record_outputs
+    o2 = dict(out, depth_values=leaf)
+    assert "grad_fn" in fast_path_refusal(record_outputs(o2), o2)
+    # a removed hook no longer observes anything: accepted again
+    h = out["depth_values"].register_hook(lambda g: g)
+    assert fast_path_refusal(rec, out) is not None
+    h.remove()
+    assert fast_path_refusal(rec, out) is None
