@@ -23,6 +23,9 @@ def __getattr__(name):
     if name in ("GridAxes", "uniform_axes", "aligned_axes"):
         from . import grid
         return getattr(grid, name)
+    if name in ("marching_cubes", "Mesh"):
+        from . import mesh
+        return getattr(mesh, name)
     if name == "RenderEngine":
         from .engine import RenderEngine
         return RenderEngine

@@ -138,6 +138,11 @@ SIGNATURES = {
     "i2sdf_sdf_grid_workspace_floats": (_I64, [_I64]),
     # plan, packed, x, y, z, nx, ny, nz, order, rot (host), trans (host), first, count, sdf_out, workspace, chunk_points, stream
     "i2sdf_sdf_grid": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _I64, _I64, _P, _P, _I64, _P]),
+    "i2sdf_marching_cubes_workspace_bytes": (_I64, [_I32, _I32, _I32]),
+    # vol, nx, ny, nz, level, workspace, counts_out, stream
+    "i2sdf_marching_cubes_count": (C.c_int, [_P, _I32, _I32, _I32, _F, _P, _P, _P]),
+    # vol, nx, ny, nz, level, spacing (host), origin (host), workspace, verts, normals, faces, cap_v, cap_f, stream
+    "i2sdf_marching_cubes_emit": (C.c_int, [_P, _I32, _I32, _I32, _F, _P, _P, _P, _P, _P, _P, _I64, _I64, _P]),
     # pred, target, channels, pixel_idx, first_pixel, n, pointlinks, n_links, pdf_max, pdf_prune, pdf, n_pdf, n_bad, stream
     "i2sdf_pdf_update": (C.c_int, [_P, _P, _I32, _P, _I64, _I64, _P, _I64, C.c_double, C.c_double, _P, _I64, _P, _P]),
     # seed, B, n_eval, n_samples, n_extra, max_iters, n_z, eik_radius, nbr_half_width, strat_u, cdf_u, extra_idx, eik_idx, eik_pts, nbr_off, stream

@@ -585,6 +585,27 @@ class I2SDFNetwork(nn.Module):
             return out.view(x.numel(), y.numel(), z.numel())
         return out
 
+    @torch.no_grad()
+    def extract_mesh(self, axes, level: float = 0.0, rot=None, trans=None, chunk: int = 1 << 21, device=None):
+        """The `level` set of the SDF on a grid as a device mesh (i2sdf_amd.mesh.Mesh: verts, faces, normals): sdf_volume(axes,
+        rot, trans) followed by i2sdf_amd.mesh.marching_cubes, with the reference's spacing (the x step for all three axes,
+        GridAxes.spacing) and its grid origin added (model/eval/recon.py:53-60).  Vertices and normals are returned in world
+        space: rot @ (v + origin) + trans and rot @ n, which on the PCA-aligned grid (rot = vecs^T, trans = s_mean) equals
+        the reference's vecs^T @ verts + grid_points[0] (:93-95).  Empty tensors when nothing crosses the level."""
+        from .mesh import Mesh, marching_cubes
+        x, y, z = (axes.x, axes.y, axes.z) if hasattr(axes, "shortest_axis_index") else axes
+        x = torch.as_tensor(x, dtype=torch.float64)
+        s = float(x[2] - x[1]) if x.numel() > 2 else float(x[1] - x[0])
+        org = [float(torch.as_tensor(a, dtype=torch.float64)[0]) for a in (x, y, z)]
+        vol = self.sdf_volume(axes, rot, trans, "volume", chunk, device=device)
+        m = marching_cubes(vol, level, (s, s, s), org)
+        if rot is None and trans is None:
+            return m
+        dev = vol.device
+        r = torch.eye(3, device=dev) if rot is None else torch.as_tensor(rot).to(dev, torch.float32).reshape(3, 3)
+        tv = torch.zeros(3, device=dev) if trans is None else torch.as_tensor(trans).to(dev, torch.float32).reshape(3)
+        return Mesh(m.verts @ r.t() + tv, m.faces, m.normals @ r.t())
+
     # ------------------------------------------------------------------------------------------
     def _extra_points(self, input, cam, dirs, z_eik, draws):
         """Eikonal / neighbour / bubble points (model/network/__init__.py:175-201)."""

@@ -594,6 +594,31 @@ int i2sdf_sdf_grid(const i2sdf_plan* plan, const float* packed, const float* x, 
                    float* sdf_out, float* workspace, int64_t chunk_points, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Marching cubes -- the zero-level mesh of an SDF volume (model/eval/recon.py:53-60,91-95, utils/plots.py:197-206 run
+ * skimage.measure.marching_cubes on the host).  vol (nx, ny, nz) device fp32, z fastest (I2SDF_GRID_ORDER_VOLUME); every
+ * axis >= 2 points.  A corner is above iff v > level (NaN is not above); the case tables are derived by
+ * i2sdf_amd/csrc/gen_mc_tables.py (ambiguous faces keep their above-level corners apart; no interior vertices).
+ *   one vertex per lattice edge whose ends straddle the level, in order of (lattice-point linear index, axis x < y < z):
+ *     verts   = origin + (i + t e) * spacing,  t = (level - v0) / (v1 - v0)                                 (V, 3) fp32
+ *     normals = -normalize((1 - t) g0 + t g1), g = np.gradient(vol, *spacing) at the edge's ends         (V, 3) fp32
+ *               (they point towards decreasing values, as scikit-image's do)
+ *   faces  (F, 3) int32 vertex indices, in order of (cell linear index, table slot); the right-hand face normal points
+ *          towards increasing values; the mesh is closed away from the volume's border.
+ * Two calls on the same stream, one workspace of i2sdf_marching_cubes_workspace_bytes(nx, ny, nz) bytes (0: shape not
+ * supported; it holds 5 bytes per lattice point):
+ *   _count  enqueues the classification and scan; counts_out (device int64[2]) | NULL <- (V, F).
+ *   _emit   same vol / level / workspace; reads (V, F) back (one stream synchronisation) and returns I2SDF_EINVAL when either
+ *           exceeds INT32_MAX, I2SDF_EWORKSPACE when cap_v < V or cap_f < F, before anything is written; otherwise enqueues the
+ *           emission.  spacing[3], origin[3] are HOST arrays.  Nothing is allocated.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t i2sdf_marching_cubes_workspace_bytes(int32_t nx, int32_t ny, int32_t nz);
+int i2sdf_marching_cubes_count(const float* vol, int32_t nx, int32_t ny, int32_t nz, float level, void* workspace, int64_t* counts_out,
+                               void* stream);
+int i2sdf_marching_cubes_emit(const float* vol, int32_t nx, int32_t ny, int32_t nz, float level, const float* spacing,
+                              const float* origin, void* workspace, float* verts, float* normals, int32_t* faces, int64_t cap_v,
+                              int64_t cap_f, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Bubble-PDF update (row N4) -- VolumeRenderSystem.update_pdf fused with the error it is fed (model/trainer/recon.py:142-152,
  * :195-199 in the initial sweep over all images, :246-252 every training step):
  *   channels == 1: v = |pred - target|                         (criterion DEPTH: depth_values vs depth image)
