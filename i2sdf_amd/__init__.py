@@ -20,10 +20,10 @@ def __getattr__(name):
     if name == "BubblePDF":
         from .bubble import BubblePDF
         return BubblePDF
-    if name in ("GridAxes", "uniform_axes", "aligned_axes"):
+    if name in ("GridAxes", "uniform_axes", "aligned_axes", "pca_frame"):
         from . import grid
         return getattr(grid, name)
-    if name in ("marching_cubes", "Mesh"):
+    if name in ("marching_cubes", "Mesh", "face_components", "largest_component", "sample_surface", "compact"):
         from . import mesh
         return getattr(mesh, name)
     if name == "RenderEngine":

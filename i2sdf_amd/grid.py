@@ -59,3 +59,39 @@ def aligned_axes(points, resolution: int, input_min: Optional[np.ndarray] = None
     step = length / (short.shape[0] - 1)
     axes = [short if a == s else np.arange(input_min[a] - eps, input_max[a] + step + eps, step) for a in range(3)]
     return GridAxes(axes[0], axes[1], axes[2], float(length), s)
+
+
+def pca_frame(points):
+    """(vecs, s_mean) of a point cloud (n, 3): s_mean its mean, the ROWS of vecs the eigenvectors of the scatter matrix
+    S = (p - s_mean)^T (p - s_mean) -- the frame of utils/plots.py:289-295 / model/eval/recon.py:64-69, in which
+    helper = vecs @ (p - s_mean) feeds aligned_axes and the grid is evaluated with rot = vecs^T, trans = s_mean.
+    The reference takes whatever order and signs the general torch.linalg.eig returns, so its frame differs between
+    libraries.  This one is one particular, fixed choice among the valid orthonormal eigen-frames: symmetric solver in fp64,
+    eigenvalues ascending, every row's sign such that its largest-magnitude entry is positive, then the reference's handedness
+    fix (det < 0: rows 1 and 2 swapped).  Mean and scatter are fp64 sums on the points' device; their twelve numbers go to
+    the host for the eigen-problem.  Returns fp32 tensors on the points' device."""
+    import torch
+    vecs, s_mean = _pca_frame_host(points)
+    dev = points.device if hasattr(points, "device") else "cpu"
+    return torch.from_numpy(vecs).to(dev, torch.float32), torch.from_numpy(s_mean).to(dev, torch.float32)
+
+
+def _pca_frame_host(points):
+    """pca_frame's (vecs, s_mean) as float64 numpy arrays: one download of twelve numbers (scatter matrix and mean)."""
+    import torch
+    p = torch.as_tensor(points)
+    if p.dim() != 2 or p.shape[1] != 3 or p.shape[0] == 0:
+        raise ValueError(f"pca_frame: points must be (n, 3) with n > 0, got {tuple(p.shape)}")
+    p = p.detach().to(torch.float64)
+    s_mean = p.mean(dim=0)
+    d = p - s_mean
+    scatter = (d.unsqueeze(2) * d.unsqueeze(1)).sum(dim=0)              # (3, 3); a plain reduction, reproducible
+    host = torch.cat([scatter, s_mean[None]]).cpu().numpy()
+    _, v = np.linalg.eigh(host[:3])                                     # ascending eigenvalues, eigenvectors in columns
+    vecs = np.ascontiguousarray(v.T)
+    for r in range(3):
+        if vecs[r, np.argmax(np.abs(vecs[r]))] < 0:
+            vecs[r] = -vecs[r]
+    if np.linalg.det(vecs) < 0:
+        vecs = vecs[[0, 2, 1]]
+    return np.ascontiguousarray(vecs), host[3].copy()

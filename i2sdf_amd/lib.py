@@ -143,6 +143,24 @@ SIGNATURES = {
     "i2sdf_marching_cubes_count": (C.c_int, [_P, _I32, _I32, _I32, _F, _P, _P, _P]),
     # vol, nx, ny, nz, level, spacing (host), origin (host), workspace, verts, normals, faces, cap_v, cap_f, stream
     "i2sdf_marching_cubes_emit": (C.c_int, [_P, _I32, _I32, _I32, _F, _P, _P, _P, _P, _P, _P, _I64, _I64, _P]),
+    "i2sdf_mesh_scan_workspace_bytes": (_I64, [_I64]),
+    "i2sdf_mesh_status": (C.c_int, [_P, _P]),
+    # faces, F, n_verts, keys, status, stream
+    "i2sdf_mesh_edge_keys": (C.c_int, [_P, _I64, _I64, _P, _P, _P]),
+    # sorted_keys, perm, F, labels, stream
+    "i2sdf_mesh_face_components": (C.c_int, [_P, _P, _I64, _P, _P]),
+    # verts, n_verts, faces, F, area, status, stream
+    "i2sdf_mesh_face_areas": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _P]),
+    # x, n_x, order, n, cdf, workspace, stream
+    "i2sdf_mesh_cumsum_f64": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _P]),
+    # sorted_labels, cdf, F, best, stream
+    "i2sdf_mesh_largest_label": (C.c_int, [_P, _P, _I64, _P, _P]),
+    # faces, mask, F, n_verts, fkeep, vflag, status, stream
+    "i2sdf_mesh_compact_mark": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _P, _P]),
+    # verts, normals, n_verts, faces, F, fkeep, fscan, vflag, vscan, out_verts, out_normals, out_faces, cap_v, cap_f, stream
+    "i2sdf_mesh_compact_gather": (C.c_int, [_P, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _P]),
+    # verts, n_verts, faces, F, cdf, u_face, u_bary, count, points, face_index, status, stream
+    "i2sdf_mesh_sample_surface": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _P, _I64, _P, _P, _P, _P]),
     # pred, target, channels, pixel_idx, first_pixel, n, pointlinks, n_links, pdf_max, pdf_prune, pdf, n_pdf, n_bad, stream
     "i2sdf_pdf_update": (C.c_int, [_P, _P, _I32, _P, _I64, _I64, _P, _I64, C.c_double, C.c_double, _P, _I64, _P, _P]),
     # seed, B, n_eval, n_samples, n_extra, max_iters, n_z, eik_radius, nbr_half_width, strat_u, cdf_u, extra_idx, eik_idx, eik_pts, nbr_off, stream

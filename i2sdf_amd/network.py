@@ -606,6 +606,37 @@ class I2SDFNetwork(nn.Module):
         tv = torch.zeros(3, device=dev) if trans is None else torch.as_tensor(trans).to(dev, torch.float32).reshape(3)
         return Mesh(m.verts @ r.t() + tv, m.faces, m.normals @ r.t())
 
+    @torch.no_grad()
+    def extract_mesh_high_res(self, resolution: int, grid_boundary=(-2.0, 2.0), level: float = 0.0, take_components: bool = True,
+                              low_resolution: int = 100, n_points: int = 10000, draws=None, generator=None, chunk: int = 1 << 21,
+                              device=None):
+        """get_surface_high_res_mesh (utils/plots.py:258-336) with no mesh data leaving the device:
+          1. marching cubes on uniform_axes(low_resolution, grid_boundary);
+          2. take_components: keep the component of the largest area (mesh.largest_component); False gives
+             SDFMeshSystem.initialize's variant (model/eval/recon.py:46-82), which samples the whole low-res mesh;
+          3. n_points area-weighted surface points (mesh.sample_surface; `draws` / `generator` as there);
+          4. their PCA frame (grid.pca_frame: one fixed choice of the eigen-frame) and helper = vecs @ (p - s_mean);
+          5. aligned_axes(helper, resolution), the SDF on that rotated grid and marching cubes again, vertices back in world space
+             (extract_mesh with rot = vecs^T, trans = s_mean).
+        Returns (Mesh, vecs, s_mean, GridAxes); when the low-res mesh is empty: (empty Mesh, None, None, None) where the reference
+        raises inside trimesh.  Host synchronisations: the counts that size the meshes, and the twelve numbers of the scatter matrix
+        and mean plus the six of the helper points' bounding box."""
+        from .grid import _pca_frame_host, aligned_axes, uniform_axes
+        from .mesh import largest_component, sample_surface
+        low = self.extract_mesh(uniform_axes(low_resolution, grid_boundary), level, chunk=chunk, device=device)
+        if take_components:
+            low = largest_component(low)
+        if low.faces.shape[0] == 0:
+            return low, None, None, None
+        pts, _ = sample_surface(low, n_points, draws=draws, generator=generator, _check=False)
+        vecs_h, mean_h = (torch.from_numpy(a).to(torch.float32) for a in _pca_frame_host(pts))      # = pca_frame(pts), kept on the host too
+        vecs, s_mean = vecs_h.to(pts.device), mean_h.to(pts.device)
+        helper = ((pts - s_mean).unsqueeze(1) * vecs.unsqueeze(0)).sum(dim=2)            # vecs @ (p - s_mean), utils/plots.py:296-297
+        box = torch.stack([helper.min(dim=0).values, helper.max(dim=0).values]).cpu().numpy()
+        axes = aligned_axes(None, resolution, input_min=box[0], input_max=box[1])
+        m = self.extract_mesh(axes, level, rot=vecs_h.t(), trans=mean_h, chunk=chunk, device=device)
+        return m, vecs, s_mean, axes
+
     # ------------------------------------------------------------------------------------------
     def _extra_points(self, input, cam, dirs, z_eik, draws):
         """Eikonal / neighbour / bubble points (model/network/__init__.py:175-201)."""

@@ -619,6 +619,52 @@ int i2sdf_marching_cubes_emit(const float* vol, int32_t nx, int32_t ny, int32_t 
                               int64_t cap_f, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Mesh operations (csrc/meshops.hip) -- what the reference runs through trimesh on the host between its two marching-cubes
+ * passes (utils/plots.py:280-297, model/eval/recon.py:61-71): split into components, keep the one with the largest area, draw
+ * area-weighted surface points.  verts / normals (V, 3) fp32, faces (F, 3) int32, all device; F, V <= INT32_MAX (else
+ * I2SDF_EINVAL); F = 0 is a no-op.  Every call only enqueues on `stream` (no allocation, no synchronisation) except
+ * i2sdf_mesh_status.  Results are bitwise reproducible: no float atomics, fixed summation order.
+ *   status   device int32 word, zeroed by the caller: a face with a vertex index outside [0, V) is never dereferenced; it
+ *            sets the word instead (such a face has area 0, is connected to nothing and is dropped by the compaction).
+ *            i2sdf_mesh_status copies it back (one stream synchronisation): I2SDF_EINVAL when set.
+ *   _edge_keys         keys[3f + c] = min(a, b) << 32 | max(a, b) for side c = (v_c, v_{c+1}) of face f           (3F) int64
+ *   _face_components   Two faces are connected when they share an edge (an unordered vertex pair), ALSO when three or more
+ *                      faces share it (trimesh's face_adjacency ignores such edges); sharing one vertex does not connect.
+ *                      The CALLER sorts the keys: sorted_keys (3F) ascending, perm (3F) int64 the position each sorted entry
+ *                      came from (entry / 3 = its face).  labels[f] <- the smallest face index of f's component   (F) int32
+ *   _face_areas        area[f] = 0.5 |(v1 - v0) x (v2 - v0)|, fp32, products and sums rounded separately          (F) fp32
+ *   _cumsum_f64        cdf[i] = sum_{j <= i} (double) x[order[j]] (order NULL: x[j]; entries outside [0, n_x) count 0), a
+ *                      reduce-then-scan in a fixed order; workspace of i2sdf_mesh_scan_workspace_bytes(n) bytes    (n) fp64
+ *   _largest_label     sorted_labels (F) ascending (a STABLE sort of the labels by the caller), cdf the running sum of the
+ *                      areas in that order.  best[0] <- bit pattern of the largest component area, best[1] <- its label
+ *                      (ties: the smaller label); (0, INT64_MAX) for F = 0                                  device int64[2]
+ *   _compact_mark      fkeep[f] <- mask[f] != 0 (mask: F bytes) and valid; vflag[v] <- 1 iff a kept face uses v   (F), (V) int32
+ *   _compact_gather    fscan / vscan = INCLUSIVE int32 running sums of fkeep / vflag (by the caller, who reads their last
+ *                      entries to size the outputs).  Kept faces in their order, re-indexed; used vertices (and normals, may be
+ *                      NULL) in their order.  Rows beyond cap_f / cap_v are not written.
+ *   _sample_surface    trimesh.sample.sample_surface with the caller's uniform draws u_face (count), u_bary (count, 2) in [0, 1):
+ *                      pick = u_face * cdf[F-1]; face = first i with cdf[i] >= pick (np.searchsorted side='left'), at most F-1;
+ *                      (a, b) = u_bary, reflected to (|a-1|, |b-1|) when a + b > 1; point = v0 + a (v1-v0) + b (v2-v0) in fp32.
+ *                      cdf = _cumsum_f64 of _face_areas.  count > 0 with F = 0 is I2SDF_EINVAL.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t i2sdf_mesh_scan_workspace_bytes(int64_t n);
+int i2sdf_mesh_status(const int32_t* status, void* stream);
+int i2sdf_mesh_edge_keys(const int32_t* faces, int64_t F, int64_t n_verts, int64_t* keys, int32_t* status, void* stream);
+int i2sdf_mesh_face_components(const int64_t* sorted_keys, const int64_t* perm, int64_t F, int32_t* labels, void* stream);
+int i2sdf_mesh_face_areas(const float* verts, int64_t n_verts, const int32_t* faces, int64_t F, float* area, int32_t* status,
+                          void* stream);
+int i2sdf_mesh_cumsum_f64(const float* x, int64_t n_x, const int64_t* order, int64_t n, double* cdf, void* workspace, void* stream);
+int i2sdf_mesh_largest_label(const int32_t* sorted_labels, const double* cdf, int64_t F, int64_t* best, void* stream);
+int i2sdf_mesh_compact_mark(const int32_t* faces, const uint8_t* mask, int64_t F, int64_t n_verts, int32_t* fkeep, int32_t* vflag,
+                            int32_t* status, void* stream);
+int i2sdf_mesh_compact_gather(const float* verts, const float* normals, int64_t n_verts, const int32_t* faces, int64_t F,
+                              const int32_t* fkeep, const int32_t* fscan, const int32_t* vflag, const int32_t* vscan,
+                              float* out_verts, float* out_normals, int32_t* out_faces, int64_t cap_v, int64_t cap_f, void* stream);
+int i2sdf_mesh_sample_surface(const float* verts, int64_t n_verts, const int32_t* faces, int64_t F, const double* cdf,
+                              const float* u_face, const float* u_bary, int64_t count, float* points, int32_t* face_index,
+                              int32_t* status, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Bubble-PDF update (row N4) -- VolumeRenderSystem.update_pdf fused with the error it is fed (model/trainer/recon.py:142-152,
  * :195-199 in the initial sweep over all images, :246-252 every training step):
  *   channels == 1: v = |pred - target|                         (criterion DEPTH: depth_values vs depth image)
