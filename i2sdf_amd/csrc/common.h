@@ -68,6 +68,8 @@ __host__ __device__ constexpr int cdiv(int a, int b) { return (a + b - 1) / b; }
 __host__ __device__ constexpr int op_chunks(int NT, int KC) { return round_up(NT * 4 + NT * KC, SC); }
 // a row-vector op: [KC weight chunks][1 scalar chunk]
 __host__ __device__ constexpr int rowvec_chunks(int KC, int nrows) { return round_up(nrows * KC + 1, SC); }
+// a transposed op (no bias): [KT*NC weight chunks]
+__host__ __device__ constexpr int bwd_op_chunks(int KT, int NC) { return round_up(KT * NC, SC); }
 
 #define I2SDF_SGB(mask, n) __builtin_amdgcn_sched_group_barrier(mask, n, 0)
 #define I2SDF_MASK_MFMA 0x008

@@ -15,21 +15,6 @@ int i2sdf_hip_check(hipError_t e, const char* what);
 
 namespace {
 
-__host__ __device__ constexpr int sdf_fwd_hidden_stages(int H, int PEC, int L, bool has_skip) {
-  int c = op_chunks(H / 32, PEC);
-  for (int l = 1; l < L - 1; ++l) c += op_chunks(H / 32, H / 8);
-  if (has_skip) c += op_chunks(H / 32, H / 8 + PEC) - op_chunks(H / 32, H / 8);
-  return c / SC;
-}
-// reverse stream: [w_sdf][W_feat^T][w_sdf][W_{L-2}^T .. W_1^T]  (W_0^T is not needed: the points carry no gradient)
-__host__ __device__ constexpr int sdf_rev_bwd_stages(int H, int F, int PEC, int L, bool has_skip) {
-  const int PT = cdiv(PEC * 8, 32);
-  int c = bwd_op_chunks(H / 32, F / 8) + 2 * rowvec_chunks(H / 8, 1);
-  for (int l = L - 2; l >= 1; --l) c += bwd_op_chunks(H / 32, H / 8);
-  if (has_skip) c += bwd_op_chunks(H / 32 + PT, H / 8) - bwd_op_chunks(H / 32, H / 8);
-  return c / SC;
-}
-
 template <int H, int F, int LF>
 __global__ __launch_bounds__(256) void sdf_bwd_kernel(SdfBwdArgs a) {
   constexpr int NT = H / 32, KC = H / 8, PEC = PE<LF>::PEC, PT = cdiv(PEC * 8, 32), FC = F / 8;
@@ -235,13 +220,6 @@ __global__ __launch_bounds__(256) void sdf_bwd_split_kernel(SdfBwdArgs a, int64_
 
 namespace {
 
-__host__ __device__ constexpr int rgb_rev_stages(int H, int F, int L) {
-  int c = rowvec_chunks(H / 8, 3);
-  for (int l = L - 2; l >= 1; --l) c += bwd_op_chunks(H / 32, H / 8);
-  c += bwd_op_chunks(F / 32, H / 8);
-  return c / SC;
-}
-
 template <int H, int F>
 __global__ __launch_bounds__(256) void rgb_bwd_kernel(RgbBwdArgs a) {
   constexpr int NT = H / 32, KC = H / 8, FT = F / 32;
@@ -387,63 +365,41 @@ extern "C" int i2sdf_sdf_backward(const i2sdf_plan* p, const float* packed, cons
     return I2SDF_EINVAL;
   const i2sdf_mlp_desc& d = p->sdf.d;
   if (d.multires != 6) return I2SDF_EINVAL;
+  // sweep 1 walks the hidden layers of the forward stream, sweep 2 the reverse stream from its start down to W_1^T
+  const Span fwd = span(p, packed, p->sdf, SPAN_FWD_HIDDEN), rev = span(p, packed, p->sdf, SPAN_REV_SWEEP2);
+  if (!fwd.n_stages || !rev.n_stages) return I2SDF_EINVAL;
   SdfBwdArgs a{};
-  const float* base = packed + p->scale_floats;
-  a.fwd = base + p->sdf.fwd_chunk0 * CHUNK_FLOATS;
-  a.rev = base + p->sdf.rev_chunk0 * CHUNK_FLOATS;
+  a.fwd = fwd.w; a.n_fwd = fwd.n_stages; a.rev = rev.w; a.n_rev = rev.n_stages;
   a.L = d.n_lin; a.skip = d.skip_layer;
   a.pts = PointSpec{points, cam, dirs, z, ldz, n_ray_pts, n_per_ray > 0 ? n_per_ray : 1};
   a.M = M; a.Mp = Mp; a.hs = hs; a.abars = abars; a.sbar = sbar; a.fbar = fbar; a.m_fbar = m_fbar; a.nbar = nbar;
   a.gus = gus; a.gpbar = gpbar; a.gas = gas; a.ga_last4 = ga_last4; a.ones4 = ones4;
   hipStream_t st = (hipStream_t)stream;
-  const unsigned grid = (unsigned)((M + PTS_PER_WG - 1) / PTS_PER_WG);
-  const bool has_skip = d.skip_layer > 0;
   if (p->H == 256 && p->F == 256) {
-    a.n_fwd = sdf_fwd_hidden_stages(256, PE<6>::PEC, d.n_lin, has_skip);
-    a.n_rev = sdf_rev_bwd_stages(256, 256, PE<6>::PEC, d.n_lin, has_skip);
-    const int64_t bulk = split_bulk_points(M, p->n_cu);
     // full workgroups in bf16x3 split arithmetic (two launches); needs at least one plain hidden layer above the skip layer
     const bool x3 = p->sdf_bwd_bf16x3 != 0 && d.n_lin >= 4 && d.skip_layer != d.n_lin - 2;
-    ChainGuard guard(p, st, x3 && i2sdf_parts_on(p));
-    auto launch3 = [&](unsigned g) {
-      SdfBwdArgs a3 = a;
-      a3.fwd = base + p->sdf.fwd3_chunk0 * CHUNK_FLOATS;
-      a3.rev = base + p->sdf.rev3_chunk0 * CHUNK_FLOATS;
-      a3.n_fwd = sdf_fwd3_hidden_stages(256, PE<6>::DIM, d.n_lin, has_skip);
-      a3.n_rev = sdf_rev3_bwd_stages(256, 256, PE<6>::PEC, d.n_lin, has_skip);
+    SdfBwdArgs a3 = a;
+    if (x3) {
+      const Span fwd3 = span(p, packed, p->sdf, SPAN_FWD3_HIDDEN), rev3 = span(p, packed, p->sdf, SPAN_REV3_SWEEP2);
+      if (!fwd3.n_stages || !rev3.n_stages) return I2SDF_EINVAL;
+      a3.fwd = fwd3.w; a3.n_fwd = fwd3.n_stages; a3.rev = rev3.w; a3.n_rev = rev3.n_stages;
       a3.kcs = sdf_blocked_points(p, M, Mp) > 0 ? KCS_BLK : KCS_PM;
       a3.p24 = (sdf_saves24(p) && a3.kcs == KCS_BLK) ? 1 : 0;
-      i2sdf_launch_sdf_bwd3(a3, g, st);
-    };
-    if (x3 && i2sdf_parts_on(p)) {      // point ranges (plan.h: PartRun): both sweeps of a range on the range's stream
-      PartRun pr;
-      i2sdf_parts_begin(p, st, M, &pr);
-      for (int q = 0; q < pr.n; ++q) {
-        if (pr.hi[q] <= pr.lo[q]) continue;
-        st = pr.st[q];
-        a.wg0 = (int)(pr.lo[q] / PTS_PER_WG);
-        launch3((unsigned)((pr.hi[q] - pr.lo[q] + PTS_PER_WG - 1) / PTS_PER_WG));
-      }
-      st = (hipStream_t)stream;
-      a.wg0 = 0;
-      i2sdf_parts_end(p, st, &pr);
-    } else if (bulk > 0) {          // full rounds + the partial last round as split-K workgroups (ksplit.h)
-      hipStream_t ts = i2sdf_tail_fork(p, st);       // tail first, on the side stream when the overlap is on (plan.h)
-      launch_lds_bytes(KS_LDS_BYTES, sdf_bwd_split_kernel<256, 256, 6>, (unsigned)((M - bulk + 31) / 32), ts, a, bulk);
-      a.M = bulk;
-      if (x3) launch3((unsigned)(bulk / PTS_PER_WG));
-      else launch_lds(sdf_bwd_kernel<256, 256, 6>, (unsigned)(bulk / PTS_PER_WG), st, a);
-      a.M = M;
-      i2sdf_tail_join(p, st, ts);
-    } else if (x3) {
-      launch3(grid);
-    } else {
-      launch_lds(sdf_bwd_kernel<256, 256, 6>, grid, st, a);
     }
+    const bool ranged = x3 && i2sdf_parts_on(p);      // point ranges (plan.h: PartRun): both sweeps of a range on the range's stream
+    ChainGuard guard(p, st, ranged);
+    auto tail = [&](hipStream_t s, int64_t m0) {       // the partial last round as split-K workgroups (ksplit.h)
+      launch_lds_bytes(KS_LDS_BYTES, sdf_bwd_split_kernel<256, 256, 6>, (unsigned)((M - m0 + 31) / 32), s, a, m0);
+    };
+    auto full = [&](hipStream_t s, int wg0, unsigned g, int64_t Mv) {
+      SdfBwdArgs x = x3 ? a3 : a;
+      x.wg0 = wg0; x.M = Mv;
+      if (x3) i2sdf_launch_sdf_bwd3(x, g, s);
+      else launch_lds(sdf_bwd_kernel<256, 256, 6>, g, s, x);
+    };
+    i2sdf_dispatch_points(p, st, M, ranged, true, TAIL_FORKED, full, tail);
   } else if (p->H == 64 && p->F == 64) {
-    a.n_fwd = sdf_fwd_hidden_stages(64, PE<6>::PEC, d.n_lin, has_skip);
-    a.n_rev = sdf_rev_bwd_stages(64, 64, PE<6>::PEC, d.n_lin, has_skip);
-    launch_lds(sdf_bwd_kernel<64, 64, 6>, grid, st, a);
+    launch_lds(sdf_bwd_kernel<64, 64, 6>, (unsigned)((M + PTS_PER_WG - 1) / PTS_PER_WG), st, a);
   } else return I2SDF_EINVAL;
   return i2sdf_hip_check(hipGetLastError(), "sdf_backward launch");
 }
@@ -454,49 +410,33 @@ extern "C" int i2sdf_rgb_backward(const i2sdf_plan* p, const float* packed, cons
   if (!p || !packed || !rgb || !rgb_bar || !rs || !gar || !ga_last || !fbar || M < 0) return I2SDF_EINVAL;
   if (Mp < M || Mp % PTS_PER_WG) return I2SDF_EINVAL;
   const i2sdf_mlp_desc& d = p->rgb.d;
+  const bool wide = d.hidden == 256 && p->F == 256, x3 = wide && p->rgb_bf16x3;
+  if (!wide && !(d.hidden == 64 && p->F == 64)) return I2SDF_EINVAL;
+  const Span rev = span(p, packed, p->rgb, SPAN_REV);
+  if (!rev.n_stages) return I2SDF_EINVAL;
   RgbBwdArgs a{};
-  a.rev = packed + p->scale_floats + p->rgb.rev_chunk0 * CHUNK_FLOATS;
+  a.rev = rev.w; a.n_rev = rev.n_stages;
   a.L = d.n_lin; a.M = M; a.Mp = Mp; a.rgb = rgb; a.rgb_bar = rgb_bar; a.rs = rs; a.gar = gar; a.ga_last = ga_last; a.fbar = fbar;
+  RgbBwdArgs a3 = a;
+  if (x3) {                                           // 16-point waves (x3h.h)
+    const Span rev3 = span(p, packed, p->rgb, SPAN_REV3H);
+    if (!rev3.n_stages) return I2SDF_EINVAL;
+    a3.rev = rev3.w; a3.n_rev = rev3.n_stages;
+    a3.kcs = rgb_blocked_points(p, M, Mp) > 0 ? KCS_BLK : KCS_PM;
+  }
   hipStream_t st = (hipStream_t)stream;
-  const unsigned grid = (unsigned)((M + PTS_PER_WG - 1) / PTS_PER_WG);
-  ChainGuard guard(p, st, d.hidden == 256 && p->F == 256 && p->rgb_bf16x3 && i2sdf_parts_on(p));
-  if (d.hidden == 256 && p->F == 256) {
-    a.n_rev = rgb_rev_stages(256, 256, d.n_lin);
-    const int64_t bulk = split_bulk_points(M, p->n_cu);
-    auto full = [&](const RgbBwdArgs& x, unsigned g) {
-      if (p->rgb_bf16x3) {
-        RgbBwdArgs x3 = x;
-        x3.rev = packed + p->scale_floats + p->rgb.rev3h_chunk0 * CHUNK_FLOATS;          // 16-point waves (x3h.h)
-        x3.n_rev = rgb_rev3h_stages(256, 256, d.n_lin);
-        x3.kcs = rgb_blocked_points(p, M, Mp) > 0 ? KCS_BLK : KCS_PM;
-        i2sdf_launch_rgb_bwd3h(x3, g, st);
-      } else {
-        launch_lds(rgb_bwd_kernel<256, 256>, g, st, x);
-      }
-    };
-    if (p->rgb_bf16x3 && i2sdf_parts_on(p)) {      // point ranges (plan.h: PartRun)
-      PartRun pr;
-      i2sdf_parts_begin(p, st, M, &pr);
-      for (int q = 0; q < pr.n; ++q) {
-        if (pr.hi[q] <= pr.lo[q]) continue;
-        st = pr.st[q];
-        RgbBwdArgs b = a;
-        b.wg0 = (int)(pr.lo[q] / PTS_PER_WG);
-        full(b, (unsigned)((pr.hi[q] - pr.lo[q] + PTS_PER_WG - 1) / PTS_PER_WG));
-      }
-      st = (hipStream_t)stream;
-      i2sdf_parts_end(p, st, &pr);
-    } else if (bulk > 0) {
-      a.M = bulk;
-      full(a, (unsigned)(bulk / PTS_PER_WG));
-      a.M = M;
-      launch_lds_bytes(KS_LDS_BYTES, rgb_bwd_split_kernel<256, 256>, (unsigned)((M - bulk + 31) / 32), st, a, bulk);
-    } else {
-      full(a, grid);
-    }
-  } else if (d.hidden == 64 && p->F == 64) {
-    a.n_rev = rgb_rev_stages(64, 64, d.n_lin);
-    launch_lds(rgb_bwd_kernel<64, 64>, grid, st, a);
-  } else return I2SDF_EINVAL;
+  const bool ranged = x3 && i2sdf_parts_on(p);
+  ChainGuard guard(p, st, ranged);
+  auto full = [&](hipStream_t s, int wg0, unsigned g, int64_t Mv) {
+    RgbBwdArgs x = x3 ? a3 : a;
+    x.wg0 = wg0; x.M = Mv;
+    if (x3) i2sdf_launch_rgb_bwd3h(x, g, s);
+    else launch_lds(rgb_bwd_kernel<256, 256>, g, s, x);
+  };
+  auto tail = [&](hipStream_t s, int64_t m0) {
+    launch_lds_bytes(KS_LDS_BYTES, rgb_bwd_split_kernel<256, 256>, (unsigned)((M - m0 + 31) / 32), s, a, m0);
+  };
+  if (wide) i2sdf_dispatch_points(p, st, M, ranged, true, TAIL_BEHIND, full, tail);
+  else launch_lds(rgb_bwd_kernel<64, 64>, (unsigned)((M + PTS_PER_WG - 1) / PTS_PER_WG), st, a);
   return i2sdf_hip_check(hipGetLastError(), "rgb_backward launch");
 }

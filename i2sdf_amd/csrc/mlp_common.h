@@ -38,20 +38,6 @@ inline void launch_lds_threads(int threads, K kern, unsigned grid, hipStream_t s
   kern<<<grid, threads, LDS_BYTES_H, st>>>(args...);
 }
 
-// Split of a launch over M points into full rounds of 128-point workgroups (one per CU) and a short tail that is run by
-// the split-K kernels (ksplit.h): returns the number of points of the bulk part (0 = no split).
-inline int64_t split_bulk_points(int64_t M, int n_cu) {
-  const int64_t n_wg = (M + PTS_PER_WG - 1) / PTS_PER_WG;
-  const int64_t full = (n_wg / n_cu) * n_cu, rem = n_wg - full;
-  if (full == 0 || rem == 0 || rem * 4 > n_cu) return 0;      // nothing to gain, or the tail would not fit one round
-  // the bulk is also where the blocked layout of the saved tensors ends, and the weight-gradient kernels pick an operand's layout once
-  // per split-M chunk: a chunk must not straddle that boundary (n_cu * 128 is a multiple of the 2048-point chunk only when n_cu % 16 == 0
-  // -- true for the 256 CUs of an MI355X, not for every partition of it).  No split then: every point goes through the full
-  // workgroups, every saved tensor is blocked throughout.
-  if ((full * PTS_PER_WG) % I2SDF_WG_CH != 0) return 0;
-  return full * PTS_PER_WG;
-}
-
 // ---- layouts of the saved per-point tensors of width 256 (hs, abars, gus, gas; rs, gar) ------------------------------
 //   point-major  [Mp][256]                          row of point m at m*256, k-chunk kc (16 floats) at +16*kc
 //   blocked      [Mp/32][16 k-chunks][32 points][16] row of point m at (m/32)*8192 + (m%32)*16, k-chunk kc at +512*kc
@@ -99,73 +85,6 @@ __device__ __forceinline__ void softplus_tiles(const f32x16 (&acc)[N], float (&h
 #pragma unroll
     for (int r = 0; r < 16; ++r) h[nt * 16 + r] = softplus100(acc[nt][r]);
 }
-
-// stage counts -- must mirror plan.cpp
-__host__ __device__ constexpr int sdf_fwd_stages(int H, int F, int PEC, int L, bool has_skip, bool full) {
-  int c = op_chunks(H / 32, PEC);
-  for (int l = 1; l < L - 1; ++l) c += op_chunks(H / 32, H / 8);
-  if (has_skip) c += op_chunks(H / 32, H / 8 + PEC) - op_chunks(H / 32, H / 8);
-  c += rowvec_chunks(H / 8, 1);
-  if (full) c += op_chunks(F / 32, H / 8);
-  return c / SC;
-}
-__host__ __device__ constexpr int sdf_fwd3_stages(int H, int PED, int L, bool has_skip) {
-  const int PE16 = cdiv(PED, 16);
-  int c = x3_op_chunks(H / 32, PE16);
-  for (int l = 1; l < L - 1; ++l) c += x3_op_chunks(H / 32, H / 16);
-  if (has_skip) c += x3_op_chunks(H / 32, H / 16 + PE16) - x3_op_chunks(H / 32, H / 16);
-  c += rowvec_chunks(H / 8, 1);
-  return c / SC;
-}
-__host__ __device__ constexpr int x3_bwd_chunks(int KT, int KC16) { return round_up(KC16 * KT * 3, SC); }
-__host__ __device__ constexpr int sdf_rev3_stages(int H, int PEC, int L, bool has_skip) {
-  const int PT = cdiv(PEC * 8, 32);
-  int c = rowvec_chunks(H / 8, 1);
-  for (int l = L - 2; l >= 1; --l) c += x3_bwd_chunks(H / 32, H / 16);
-  if (has_skip) c += x3_bwd_chunks(PT, H / 16);
-  c += x3_bwd_chunks(PT, H / 16);
-  return c / SC;
-}
-// backward sweep 1 walks the hidden layers of the bf16x3 forward stream; sweep 2 the reverse stream from its start down to W_1^T
-__host__ __device__ constexpr int sdf_fwd3_hidden_stages(int H, int PED, int L, bool has_skip) {
-  return sdf_fwd3_stages(H, PED, L, has_skip) - rowvec_chunks(H / 8, 1) / SC;
-}
-__host__ __device__ constexpr int sdf_rev3_bwd_stages(int H, int F, int PEC, int L, bool has_skip) {
-  const int PT = cdiv(PEC * 8, 32);
-  int c = 2 * rowvec_chunks(H / 8, 1) + x3_bwd_chunks(H / 32, F / 16);
-  for (int l = L - 2; l >= 1; --l) c += x3_bwd_chunks(H / 32, H / 16);
-  if (has_skip) c += x3_bwd_chunks(PT, H / 16);
-  return c / SC;
-}
-// ---- 16-point-wave family (x3h.h): same ops, 16-row tiles / 32-wide k-chunks -- must mirror plan.cpp
-__host__ __device__ constexpr int sdf_fwd3h_stages(int H, int PED, int L, bool has_skip, int PL = 3) {
-  const int PE32 = cdiv(PED, 32);
-  int c = x3h_op_chunks(H / 16, PE32, PL);
-  for (int l = 1; l < L - 1; ++l) c += x3h_op_chunks(H / 16, H / 32, PL);
-  if (has_skip) c += x3h_op_chunks(H / 16, H / 32 + PE32, PL) - x3h_op_chunks(H / 16, H / 32, PL);
-  c += rowvec_h_chunks(H / 16, 1);
-  return c / SCH;
-}
-__host__ __device__ constexpr int sdf_fwd3h_train_stages(int H, int F, int PED, int L, bool has_skip, bool full) {
-  return sdf_fwd3h_stages(H, PED, L, has_skip) + (full ? x3h_op_chunks(F / 16, H / 32) / SCH : 0);
-}
-__host__ __device__ constexpr int rgb_fwd3h_stages(int H, int F, int PEDV, int L) {
-  return (x3h_op_chunks(H / 16, cdiv(PEDV, 32) + F / 32) + (L - 2) * x3h_op_chunks(H / 16, H / 32) + rowvec_h_chunks(H / 16, 3)) / SCH;
-}
-__host__ __device__ constexpr int rgb_rev3h_stages(int H, int F, int L) {
-  return (rowvec_h_chunks(H / 16, 3) + (L - 2) * x3h_bwd_chunks(H / 16, H / 32) + x3h_bwd_chunks(F / 16, H / 32)) / SCH;
-}
-__host__ __device__ constexpr int bwd_op_chunks(int KT, int NC) { return round_up(KT * NC, SC); }
-// reverse stream from the w_sdf row vector to W_0^T (the d sdf/dx chain); PT = tiles of the PE space
-__host__ __device__ constexpr int sdf_rev_stages(int H, int PEC, int L, bool has_skip) {
-  const int PT = cdiv(PEC * 8, 32);
-  int c = rowvec_chunks(H / 8, 1);
-  for (int l = L - 2; l >= 1; --l) c += bwd_op_chunks(H / 32, H / 8);
-  if (has_skip) c += bwd_op_chunks(H / 32 + PT, H / 8) - bwd_op_chunks(H / 32, H / 8);
-  c += bwd_op_chunks(PT, H / 8);
-  return c / SC;
-}
-__host__ __device__ constexpr int sdf_rev_feat_stages(int H, int F) { return bwd_op_chunks(H / 32, F / 8) / SC; }
 
 // transposed dense op without bias: stream layout [KT*NC weight chunks] padded to stages
 //   MODE 1: acc = W^T in     MODE 2: acc += W^T in

@@ -70,39 +70,39 @@ template <int H, int F, int LF>
 int launch_sdf_fwd(const i2sdf_plan* p, const float* packed, PointSpec points, const int* skip_flag, int64_t M, float* sdf_out,
                    float* feat_out, int64_t ld_feat, hipStream_t st, bool sampler_pass = false) {
   const i2sdf_mlp_desc& d = p->sdf.d;
-  const float* stream = packed + p->scale_floats + p->sdf.fwd_chunk0 * CHUNK_FLOATS;
   const bool full = feat_out != nullptr;
-  if (!full && sdf_out != nullptr && p->sdf_fwd_bf16x3 && H == 256 && p->sdf.fwd3h_chunks > 0) {
+  const unsigned grid = (unsigned)((M + PTS_PER_WG - 1) / PTS_PER_WG);
+  if (!full && sdf_out != nullptr && p->sdf_fwd_bf16x3 && H == 256 && span_chunks(p->sdf, SPAN_FWD3H) > 0) {
     // 256-wide nets: 16-point waves, two per SIMD (x3h.h); the sampler's passes with two split planes under I2SDF_OPT_SAMPLER_BF16X2
-    const int PL = (sampler_pass && p->sampler_bf16x2 && p->sdf.fwd2h_chunks > 0) ? 2 : 3;
-    const float* s3 = packed + p->scale_floats + (PL == 2 ? p->sdf.fwd2h_chunk0 : p->sdf.fwd3h_chunk0) * CHUNK_FLOATS;
-    const int ns3 = sdf_fwd3h_stages(H, PE<LF>::DIM, d.n_lin, d.skip_layer > 0, PL);
-    i2sdf_launch_sdf_fwd3h(s3, ns3, d.n_lin, d.skip_layer, points, skip_flag, M, sdf_out, PL, st);
+    const int PL = (sampler_pass && p->sampler_bf16x2 && span_chunks(p->sdf, SPAN_FWD2H) > 0) ? 2 : 3;
+    const Span s3 = span(p, packed, p->sdf, PL == 2 ? SPAN_FWD2H : SPAN_FWD3H_SDF);
+    if (!s3.n_stages) return I2SDF_EINVAL;
+    i2sdf_launch_sdf_fwd3h(s3.w, s3.n_stages, d.n_lin, d.skip_layer, points, skip_flag, M, sdf_out, PL, st);
     return i2sdf_hip_check(hipGetLastError(), "sdf_forward (bf16x3, 16-point waves) launch");
   }
-  if (!full && sdf_out != nullptr && p->sdf_fwd_bf16x3 && H == 64 && p->sdf.fwd3_chunks > 0) {
-    const float* s3 = packed + p->scale_floats + p->sdf.fwd3_chunk0 * CHUNK_FLOATS;
-    const int ns3 = sdf_fwd3_stages(H, PE<LF>::DIM, d.n_lin, d.skip_layer > 0);
-    i2sdf_launch_sdf_fwd3(H, s3, ns3, d.n_lin, d.skip_layer, points, skip_flag, M, sdf_out, (unsigned)((M + PTS_PER_WG - 1) / PTS_PER_WG), st);
+  if (!full && sdf_out != nullptr && p->sdf_fwd_bf16x3 && H == 64 && span_chunks(p->sdf, SPAN_FWD3) > 0) {
+    const Span s3 = span(p, packed, p->sdf, SPAN_FWD3);
+    if (!s3.n_stages) return I2SDF_EINVAL;
+    i2sdf_launch_sdf_fwd3(H, s3.w, s3.n_stages, d.n_lin, d.skip_layer, points, skip_flag, M, sdf_out, grid, st);
     return i2sdf_hip_check(hipGetLastError(), "sdf_forward (bf16x3) launch");
   }
-  if (full && p->sdf_fwd_bf16x3 && H == 256 && F == 256 && p->sdf.fwd3h_chunks > 0) {
+  if (full && p->sdf_fwd_bf16x3 && H == 256 && F == 256 && span_chunks(p->sdf, SPAN_FWD3H) > 0) {
     // [sdf | feature] rows (ImplicitNetwork.forward: the meshing callers, model/eval/recon.py:51,90, utils/plots.py:52): the 16-point-wave
     // forward of the training path without its saves -- the same kernel, so the 257 columns are the values a training step computes
+    const Span s3 = span(p, packed, p->sdf, SPAN_FWD3H);
+    if (!s3.n_stages || skip_flag != nullptr) return I2SDF_EINVAL;      // (the sampler never asks for features)
     SdfTrainFwdArgs a{};
-    a.fwd = packed + p->scale_floats + p->sdf.fwd3h_chunk0 * CHUNK_FLOATS;
-    a.n_fwd = sdf_fwd3h_train_stages(256, 256, PE<LF>::DIM, d.n_lin, d.skip_layer > 0, true);
+    a.fwd = s3.w; a.n_fwd = s3.n_stages;
     a.L = d.n_lin; a.skip = d.skip_layer; a.pts = points; a.M = M; a.Mp = M; a.sdf = sdf_out; a.feat = feat_out; a.ldf = ld_feat;
-    if (skip_flag != nullptr) return I2SDF_EINVAL;      // (the sampler never asks for features)
-    i2sdf_launch_train_fwd3h(a, (unsigned)((M + PTS_PER_WG - 1) / PTS_PER_WG), st);
+    i2sdf_launch_train_fwd3h(a, grid, st);
     return i2sdf_hip_check(hipGetLastError(), "sdf_forward (features, bf16x3, 16-point waves) launch");
   }
-  const int ns = sdf_fwd_stages(H, F, PE<LF>::PEC, d.n_lin, d.skip_layer > 0, full);
-  const unsigned grid = (unsigned)((M + PTS_PER_WG - 1) / PTS_PER_WG);
+  const Span s = span(p, packed, p->sdf, full ? SPAN_FWD : SPAN_FWD_SDF);
+  if (!s.n_stages) return I2SDF_EINVAL;
   if (full)
-    launch_lds(sdf_fwd_kernel<H, F, LF, true>, grid, st, stream, ns, d.n_lin, d.skip_layer, points, skip_flag, M, sdf_out, feat_out, ld_feat);
+    launch_lds(sdf_fwd_kernel<H, F, LF, true>, grid, st, s.w, s.n_stages, d.n_lin, d.skip_layer, points, skip_flag, M, sdf_out, feat_out, ld_feat);
   else
-    launch_lds(sdf_fwd_kernel<H, F, LF, false>, grid, st, stream, ns, d.n_lin, d.skip_layer, points, skip_flag, M, sdf_out, nullptr, 0);
+    launch_lds(sdf_fwd_kernel<H, F, LF, false>, grid, st, s.w, s.n_stages, d.n_lin, d.skip_layer, points, skip_flag, M, sdf_out, nullptr, 0);
   return i2sdf_hip_check(hipGetLastError(), "sdf_forward launch");
 }
 

@@ -239,13 +239,6 @@ __global__ __launch_bounds__(256) void sdf_train_fwd_split_kernel(SdfTrainFwdArg
 
 namespace {
 
-__host__ __device__ constexpr int rgb_fwd_stages(int H, int F, int PECV, int L) {
-  int c = op_chunks(H / 32, PECV + F / 8);
-  for (int l = 1; l < L - 1; ++l) c += op_chunks(H / 32, H / 8);
-  c += rowvec_chunks(H / 8, 3);
-  return c / SC;
-}
-
 template <int H, int F, int LFV>
 __global__ __launch_bounds__(256) void rgb_fwd_kernel(RgbFwdArgs a) {
   constexpr int NT = H / 32, KC = H / 8, PECV = PE<LFV>::PEC, FC = F / 8;
@@ -369,79 +362,49 @@ extern "C" int i2sdf_sdf_forward_grad(const i2sdf_plan* p, const float* packed, 
   if (grad && !hs) return I2SDF_EINVAL;          // the reverse chain re-reads h_l
   const i2sdf_mlp_desc& d = p->sdf.d;
   if (d.multires != 6) return I2SDF_EINVAL;
+  const bool wide = p->H == 256 && p->F == 256;
+  if (!wide && !(p->H == 64 && p->F == 64)) return I2SDF_EINVAL;
+  const Span fwd = span(p, packed, p->sdf, feat ? SPAN_FWD : SPAN_FWD_SDF), rev = span(p, packed, p->sdf, SPAN_REV_CHAIN);
+  if (!fwd.n_stages || !rev.n_stages) return I2SDF_EINVAL;
   SdfTrainFwdArgs a{};
-  const float* base = packed + p->scale_floats;
-  a.fwd = base + p->sdf.fwd_chunk0 * CHUNK_FLOATS;
-  a.rev = base + p->sdf.rev_wsdf_chunk * CHUNK_FLOATS;
+  a.fwd = fwd.w; a.n_fwd = fwd.n_stages; a.rev = rev.w; a.n_rev = rev.n_stages;
   a.L = d.n_lin; a.skip = d.skip_layer;
   a.pts = PointSpec{points, cam, dirs, z, ldz, n_ray_pts, n_per_ray > 0 ? n_per_ray : 1};
   a.M = M; a.Mp = Mp; a.sdf = sdf; a.feat = feat; a.grad = grad; a.hs = hs; a.abars = abars; a.pe_save = pe_save;
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned grid = (unsigned)((M + PTS_PER_WG - 1) / PTS_PER_WG);
-  const bool has_skip = d.skip_layer > 0;
-#define LAUNCH(HH, FF, G_)                                                                           \
-  do {                                                                                               \
-    a.n_fwd = sdf_fwd_stages(HH, FF, PE<6>::PEC, d.n_lin, has_skip, feat != nullptr);                \
-    a.n_rev = sdf_rev_stages(HH, PE<6>::PEC, d.n_lin, has_skip);                                     \
-    if (grad) launch_lds(sdf_train_fwd_kernel<HH, FF, 6, true>, G_, st, a);                          \
-    else launch_lds(sdf_train_fwd_kernel<HH, FF, 6, false>, G_, st, a);                              \
-  } while (0)
   // full workgroups in bf16x3 split arithmetic: the forward with saves on 16-point waves (x3h.h, mlp_x3h.hip), the d sdf/dx chain on
   // 32-point waves (x3.h, mlp_x3.hip) -- both read / write the same saved tensors; the split-K tail keeps the fp32 MFMA kernel
-#define LAUNCH3(G_)                                                                                  \
-  do {                                                                                               \
-    SdfTrainFwdArgs a3 = a;                                                                          \
-    a3.fwd = base + p->sdf.fwd3h_chunk0 * CHUNK_FLOATS;                                              \
-    a3.rev = base + p->sdf.rev3_wsdf_chunk * CHUNK_FLOATS;                                           \
-    a3.n_fwd = sdf_fwd3h_train_stages(256, 256, PE<6>::DIM, d.n_lin, has_skip, feat != nullptr);     \
-    a3.n_rev = sdf_rev3_stages(256, PE<6>::PEC, d.n_lin, has_skip);                                  \
-    a3.kcs = sdf_blocked_points(p, M, Mp, feat != nullptr) > 0 ? KCS_BLK : KCS_PM;                   \
-    a3.p24 = (sdf_saves24(p) && a3.kcs == KCS_BLK && abars != nullptr) ? 1 : 0;                      \
-    i2sdf_launch_train_fwd3h(a3, G_, st);                                                            \
-    if (grad) i2sdf_launch_igrad3(a3, G_, st);                                                       \
-  } while (0)
-  const bool x3 = p->train_fwd_bf16x3 != 0 && p->H == 256 && p->F == 256 && d.n_lin >= 4 && d.skip_layer != d.n_lin - 2;
-  ChainGuard guard(p, st, x3 && i2sdf_parts_on(p));
-  if (x3 && i2sdf_parts_on(p)) {
-    // point ranges (plan.h: PartRun): one launch pair per range, each on the range's own stream; no split-K tail
-    PartRun pr;
-    i2sdf_parts_begin(p, st, M, &pr);
-    for (int q = 0; q < pr.n; ++q) {
-      if (pr.hi[q] <= pr.lo[q]) continue;
-      st = pr.st[q];
-      a.wg0 = (int)(pr.lo[q] / PTS_PER_WG);
-      LAUNCH3((unsigned)((pr.hi[q] - pr.lo[q] + PTS_PER_WG - 1) / PTS_PER_WG));
-    }
-    st = (hipStream_t)stream;
-    a.wg0 = 0;
-    i2sdf_parts_end(p, st, &pr);
-  } else if (p->H == 256 && p->F == 256) {
-    const int64_t bulk = split_bulk_points(M, p->n_cu);
-    if (bulk > 0 && feat != nullptr) {      // full rounds + the partial last round as split-K workgroups (ksplit.h)
-      const int64_t M_all = a.M;
-      const unsigned tg = (unsigned)((M_all - bulk + 31) / 32);
-      {                                      // tail first, on the side stream when the overlap is on (plan.h)
-        auto t = a;
-        t.n_fwd = sdf_fwd_stages(256, 256, PE<6>::PEC, d.n_lin, has_skip, feat != nullptr);
-        t.n_rev = sdf_rev_stages(256, PE<6>::PEC, d.n_lin, has_skip);
-        hipStream_t ts = i2sdf_tail_fork(p, st);
-        if (grad) launch_lds_bytes(KS_LDS_BYTES, sdf_train_fwd_split_kernel<256, 256, 6, true>, tg, ts, t, bulk);
-        else launch_lds_bytes(KS_LDS_BYTES, sdf_train_fwd_split_kernel<256, 256, 6, false>, tg, ts, t, bulk);
-        a.M = bulk;
-        if (x3) LAUNCH3((unsigned)(bulk / PTS_PER_WG));
-        else LAUNCH(256, 256, (unsigned)(bulk / PTS_PER_WG));
-        a.M = M_all;
-        i2sdf_tail_join(p, st, ts);
-      }
-    } else if (x3) {
-      LAUNCH3(grid);
+  const bool x3 = p->train_fwd_bf16x3 != 0 && wide && d.n_lin >= 4 && d.skip_layer != d.n_lin - 2;
+  SdfTrainFwdArgs a3 = a;
+  if (x3) {
+    const Span fwd3 = span(p, packed, p->sdf, feat ? SPAN_FWD3H : SPAN_FWD3H_SDF), rev3 = span(p, packed, p->sdf, SPAN_REV3_CHAIN);
+    if (!fwd3.n_stages || !rev3.n_stages) return I2SDF_EINVAL;
+    a3.fwd = fwd3.w; a3.n_fwd = fwd3.n_stages; a3.rev = rev3.w; a3.n_rev = rev3.n_stages;
+    a3.kcs = sdf_blocked_points(p, M, Mp, feat != nullptr) > 0 ? KCS_BLK : KCS_PM;
+    a3.p24 = (sdf_saves24(p) && a3.kcs == KCS_BLK && abars != nullptr) ? 1 : 0;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const bool ranged = x3 && i2sdf_parts_on(p);      // point ranges (plan.h: PartRun): one launch pair per range; no split-K tail
+  ChainGuard guard(p, st, ranged);
+  auto tail = [&](hipStream_t s, int64_t m0) {       // the partial last round as split-K workgroups (ksplit.h)
+    const unsigned g = (unsigned)((M - m0 + 31) / 32);
+    if (grad) launch_lds_bytes(KS_LDS_BYTES, sdf_train_fwd_split_kernel<256, 256, 6, true>, g, s, a, m0);
+    else launch_lds_bytes(KS_LDS_BYTES, sdf_train_fwd_split_kernel<256, 256, 6, false>, g, s, a, m0);
+  };
+  auto full = [&](hipStream_t s, int wg0, unsigned g, int64_t Mv) {
+    SdfTrainFwdArgs x = x3 ? a3 : a;
+    x.wg0 = wg0; x.M = Mv;
+    if (x3) {
+      i2sdf_launch_train_fwd3h(x, g, s);
+      if (grad) i2sdf_launch_igrad3(x, g, s);
+    } else if (wide) {
+      if (grad) launch_lds(sdf_train_fwd_kernel<256, 256, 6, true>, g, s, x);
+      else launch_lds(sdf_train_fwd_kernel<256, 256, 6, false>, g, s, x);
     } else {
-      LAUNCH(256, 256, grid);
+      if (grad) launch_lds(sdf_train_fwd_kernel<64, 64, 6, true>, g, s, x);
+      else launch_lds(sdf_train_fwd_kernel<64, 64, 6, false>, g, s, x);
     }
-  } else if (p->H == 64 && p->F == 64) LAUNCH(64, 64, grid);
-  else return I2SDF_EINVAL;
-#undef LAUNCH
-#undef LAUNCH3
+  };
+  i2sdf_dispatch_points(p, st, M, ranged, wide && feat != nullptr, TAIL_FORKED, full, tail);
   return i2sdf_hip_check(hipGetLastError(), "sdf_forward_grad launch");
 }
 
@@ -452,52 +415,35 @@ extern "C" int i2sdf_rgb_forward(const i2sdf_plan* p, const float* packed, const
   if (Mp < M || Mp % PTS_PER_WG) return I2SDF_EINVAL;
   const i2sdf_mlp_desc& d = p->rgb.d;
   if (d.multires != 4) return I2SDF_EINVAL;
+  const bool wide = d.hidden == 256 && p->F == 256, x3 = wide && p->rgb_bf16x3;
+  if (!wide && !(d.hidden == 64 && p->F == 64)) return I2SDF_EINVAL;
+  const Span fwd = span(p, packed, p->rgb, SPAN_FWD);
+  if (!fwd.n_stages) return I2SDF_EINVAL;
   RgbFwdArgs a{};
-  a.fwd = packed + p->scale_floats + p->rgb.fwd_chunk0 * CHUNK_FLOATS;
+  a.fwd = fwd.w; a.n_fwd = fwd.n_stages;
   a.L = d.n_lin; a.dirs = dirs; a.n_per_ray = n_per_ray; a.feat = feat; a.M = M; a.Mp = Mp; a.rgb = rgb; a.rs = rs; a.pev_save = pev_save;
+  // full workgroups optionally in bf16x3 split arithmetic (mlp_x3h.hip); the split-K tail keeps the fp32 MFMA kernel
+  RgbFwdArgs a3 = a;
+  if (x3) {
+    const Span fwd3 = span(p, packed, p->rgb, SPAN_FWD3H);
+    if (!fwd3.n_stages) return I2SDF_EINVAL;
+    a3.fwd = fwd3.w; a3.n_fwd = fwd3.n_stages;
+    a3.kcs = rgb_blocked_points(p, M, Mp) > 0 ? KCS_BLK : KCS_PM;
+  }
   hipStream_t st = (hipStream_t)stream;
-  const unsigned grid = (unsigned)((M + PTS_PER_WG - 1) / PTS_PER_WG);
-  ChainGuard guard(p, st, d.hidden == 256 && p->F == 256 && p->rgb_bf16x3 && i2sdf_parts_on(p));
-  if (d.hidden == 256 && p->F == 256) {
-    a.n_fwd = rgb_fwd_stages(256, 256, PE<4>::PEC, d.n_lin);
-    const int64_t bulk = split_bulk_points(M, p->n_cu);
-    // full workgroups optionally in bf16x3 split arithmetic (mlp_x3.hip); the split-K tail keeps the fp32 MFMA kernel
-    auto full = [&](const RgbFwdArgs& x, unsigned g) {
-      if (p->rgb_bf16x3) {
-        RgbFwdArgs x3 = x;
-        x3.kcs = rgb_blocked_points(p, M, Mp) > 0 ? KCS_BLK : KCS_PM;
-        x3.fwd = packed + p->scale_floats + p->rgb.fwd3h_chunk0 * CHUNK_FLOATS;
-        x3.n_fwd = rgb_fwd3h_stages(256, 256, PE<4>::DIM, d.n_lin);
-        i2sdf_launch_rgb_fwd3h(x3, g, st);
-      } else {
-        launch_lds(rgb_fwd_kernel<256, 256, 4>, g, st, x);
-      }
-    };
-    if (p->rgb_bf16x3 && i2sdf_parts_on(p)) {      // point ranges (plan.h: PartRun)
-      PartRun pr;
-      i2sdf_parts_begin(p, st, M, &pr);
-      for (int q = 0; q < pr.n; ++q) {
-        if (pr.hi[q] <= pr.lo[q]) continue;
-        st = pr.st[q];
-        RgbFwdArgs b = a;
-        b.wg0 = (int)(pr.lo[q] / PTS_PER_WG);
-        full(b, (unsigned)((pr.hi[q] - pr.lo[q] + PTS_PER_WG - 1) / PTS_PER_WG));
-      }
-      st = (hipStream_t)stream;
-      i2sdf_parts_end(p, st, &pr);
-    } else if (bulk > 0) {          // full rounds with one 32-point tile per wave, the partial last round as split-K workgroups
-      RgbFwdArgs b = a;
-      b.M = bulk;
-      full(b, (unsigned)(bulk / PTS_PER_WG));
-      // (no side stream here: this tail is 32 short workgroups, the fork/join costs more than the overlap gains -- measured)
-      launch_lds_bytes(KS_LDS_BYTES, rgb_fwd_split_kernel<256, 256, 4>, (unsigned)((M - bulk + 31) / 32), st, a, bulk);
-    } else {
-      full(a, grid);
-    }
-  } else if (d.hidden == 64 && p->F == 64) {
-    a.n_fwd = rgb_fwd_stages(64, 64, PE<4>::PEC, d.n_lin);
-    launch_lds(rgb_fwd_kernel<64, 64, 4>, grid, st, a);
-  } else return I2SDF_EINVAL;
+  const bool ranged = x3 && i2sdf_parts_on(p);
+  ChainGuard guard(p, st, ranged);
+  auto full = [&](hipStream_t s, int wg0, unsigned g, int64_t Mv) {
+    RgbFwdArgs x = x3 ? a3 : a;
+    x.wg0 = wg0; x.M = Mv;
+    if (x3) i2sdf_launch_rgb_fwd3h(x, g, s);
+    else launch_lds(rgb_fwd_kernel<256, 256, 4>, g, s, x);
+  };
+  auto tail = [&](hipStream_t s, int64_t m0) {
+    launch_lds_bytes(KS_LDS_BYTES, rgb_fwd_split_kernel<256, 256, 4>, (unsigned)((M - m0 + 31) / 32), s, a, m0);
+  };
+  if (wide) i2sdf_dispatch_points(p, st, M, ranged, true, TAIL_BEHIND, full, tail);
+  else launch_lds(rgb_fwd_kernel<64, 64, 4>, (unsigned)((M + PTS_PER_WG - 1) / PTS_PER_WG), st, a);
   return i2sdf_hip_check(hipGetLastError(), "rgb_forward launch");
 }
 
@@ -572,18 +518,20 @@ extern "C" int i2sdf_light_forward(const i2sdf_plan* p, const float* packed, con
   if (Mp < M || Mp % PTS_PER_WG) return I2SDF_EINVAL;
   LightArgs a{};
   const int HL = p->light.d.hidden, F = p->F;
-  a.fwd = packed + p->scale_floats + p->light.fwd_chunk0 * CHUNK_FLOATS;
-  a.n_fwd = (op_chunks(HL / 32, F / 8) + rowvec_chunks(HL / 8, 1)) / SC;
+  const Span fwd = span(p, packed, p->light, SPAN_FWD);
+  if (!fwd.n_stages) return I2SDF_EINVAL;
+  a.fwd = fwd.w; a.n_fwd = fwd.n_stages;
   a.feat = feat; a.M = M; a.Mp = Mp; a.lm = lm; a.hl = hl;
   hipStream_t st = (hipStream_t)stream;
   // the head's kernels are never cut into point ranges: called INSIDE a chain (a C caller may; the module calls it outside) the entry
   // point joins the ranges into `st` first -- `feat` is written by the ranges of i2sdf_sdf_forward_grad -- and fences them behind itself
   ChainGuard guard(p, st, false);
   const unsigned grid = (unsigned)((M + PTS_PER_WG - 1) / PTS_PER_WG);
-  if (p->rgb_bf16x3 && HL == 128 && F == 256 && p->light.fwd3h_chunks > 0) {      // bf16x3 split arithmetic with the radiance net's option
+  if (p->rgb_bf16x3 && HL == 128 && F == 256 && span_chunks(p->light, SPAN_FWD3H) > 0) {      // bf16x3 split arithmetic with the radiance net's option
+    const Span fwd3 = span(p, packed, p->light, SPAN_FWD3H);
+    if (!fwd3.n_stages) return I2SDF_EINVAL;
     LightFwd3hArgs x{};
-    x.fwd = packed + p->scale_floats + p->light.fwd3h_chunk0 * CHUNK_FLOATS;
-    x.n_fwd = (int)(p->light.fwd3h_chunks / SCH);
+    x.fwd = fwd3.w; x.n_fwd = fwd3.n_stages;
     x.feat = feat; x.M = M; x.lm = lm; x.hl = hl;
     i2sdf_launch_light_fwd3h(x, (unsigned)((M + 8 * HP - 1) / (8 * HP)), st);
     return i2sdf_hip_check(hipGetLastError(), "light_forward launch");
@@ -601,8 +549,9 @@ extern "C" int i2sdf_light_backward(const i2sdf_plan* p, const float* packed, co
   if (Mp < M || Mp % PTS_PER_WG) return I2SDF_EINVAL;
   LightArgs a{};
   const int HL = p->light.d.hidden;
-  a.rev = packed + p->scale_floats + p->light.rev_chunk0 * CHUNK_FLOATS;
-  a.n_rev = rowvec_chunks(HL / 8, 1) / SC;
+  const Span rev = span(p, packed, p->light, SPAN_REV);
+  if (!rev.n_stages) return I2SDF_EINVAL;
+  a.rev = rev.w; a.n_rev = rev.n_stages;
   a.M = M; a.Mp = Mp; a.lm = const_cast<float*>(lm); a.lm_bar = lm_bar; a.hl = const_cast<float*>(hl); a.gal0 = gal0; a.gal_last = gal_last;
   hipStream_t st = (hipStream_t)stream;
   ChainGuard guard(p, st, false);         // as in i2sdf_light_forward: whole-batch launches on `st`, joined / fenced when called inside a chain

@@ -1,6 +1,7 @@
 // Plan construction (host) + the C-ABI entry points that do not launch MLP kernels.
 #include <hip/hip_runtime.h>
 #include <string.h>
+#include <initializer_list>
 #include <string>
 #include "plan.h"
 #include <stdlib.h>
@@ -32,6 +33,7 @@ extern "C" const char* i2sdf_strerror(int code) {
 namespace {
 
 constexpr int32_t HUGE_SPLIT = 1 << 30;
+constexpr float RS2 = 0.70710678118654752440f;      // 1/sqrt(2) of the skip concatenation
 
 struct Builder {
   std::vector<Seg>& segs;
@@ -58,86 +60,75 @@ Seg base_seg(const NetPlan& np, int l, int type) {
 int pe_dim(const i2sdf_mlp_desc& d) { return d.multires > 0 ? d.d_in + 2 * d.d_in * d.multires : d.d_in; }
 int pe_chunks(const i2sdf_mlp_desc& d) { return cdiv(pe_dim(d), 8); }
 
-// dense forward op: [NT*4 bias chunks][NT*KC weight chunks] padded to stages
-void emit_dense_fwd(Builder& b, const NetPlan& np, int l, int NT, int KC, ColMap cm, int row_off, int nrows) {
-  Seg sb = base_seg(np, l, SEG_BIAS);
-  sb.NT = NT; sb.KC = 4; sb.nchunks = NT * 4; sb.used = NT * 4; sb.row_off = row_off; sb.nrows = nrows;
+ColMap cols(int n) { return ColMap{HUGE_SPLIT, 0, n, 0, 0}; }      // the first n columns, no split
+
+// A kernel family's forward ops as data: the segment types its kernels read, its tile geometry, its split planes.
+struct Family {
+  int32_t bias_type, w_type, rowvec_type;
+  int tile_rows;        // rows of an output tile
+  int k_width;          // columns of a k-chunk of a dense op
+  int rv_width;         // columns of a chunk of a row-vector op
+  int bias_chunks;      // bias chunks per output tile
+  int planes;           // chunks per (tile, k-chunk): 1 = fp32, 3 / 2 = bf16 split planes, K-outer order
+  bool fold_skip;       // the 1/sqrt(2) of the skip concatenation is folded into that layer's weights (fp32: the kernel applies it)
+};
+constexpr Family FP32{SEG_BIAS, SEG_WFWD, SEG_ROWVEC, 32, 8, 8, 4, 1, false};
+constexpr Family X3{SEG_BIAS, SEG_WFWD3, SEG_ROWVEC, 32, 16, 8, 4, 3, true};             // x3.h: 32-point waves
+constexpr Family X3H{SEG_BIAS_H, SEG_WFWD3H, SEG_ROWVEC_H, 16, 32, 16, 1, 3, true};      // x3h.h: 16-point waves
+constexpr Family X2H{SEG_BIAS_H, SEG_WFWD2H, SEG_ROWVEC_H, 16, 32, 16, 1, 2, true};      // the same with the two leading planes only (dense_x3h<..., PL = 2>)
+
+// dense forward op: [NT * bias_chunks bias chunks][NT * KC * planes weight chunks] padded to stages
+void emit_dense(Builder& b, const NetPlan& np, int l, const Family& f, int NT, int KC, ColMap cm, float mult, int row_off, int nrows) {
+  Seg sb = base_seg(np, l, f.bias_type);
+  sb.NT = NT; sb.KC = f.bias_chunks; sb.nchunks = sb.used = NT * f.bias_chunks; sb.row_off = row_off; sb.nrows = nrows;
   b.add(sb);
-  Seg sw = base_seg(np, l, SEG_WFWD);
-  sw.NT = NT; sw.KC = KC; sw.used = NT * KC; sw.nchunks = op_chunks(NT, KC) - NT * 4; sw.cm = cm;
-  sw.row_off = row_off; sw.nrows = nrows;
+  Seg sw = base_seg(np, l, f.w_type);
+  sw.NT = NT; sw.KC = KC; sw.used = NT * KC * f.planes; sw.cm = cm; sw.mult = mult; sw.row_off = row_off; sw.nrows = nrows;
+  sw.nchunks = (f.w_type == SEG_WFWD ? op_chunks(NT, KC) : f.w_type == SEG_WFWD3 ? x3_op_chunks(NT, KC) : x3h_op_chunks(NT, KC, f.planes)) - sb.nchunks;
   b.add(sw);
 }
-// transposed op (no bias): out tiles over the layer's input space, reduction over its output rows
-void emit_dense_bwd(Builder& b, const NetPlan& np, int l, int KT, int NC, ColMap cm, int row_off, int nrows) {
-  Seg sw = base_seg(np, l, SEG_WBWD);
-  sw.NT = KT; sw.KC = NC; sw.used = KT * NC; sw.nchunks = round_up(KT * NC, SC); sw.cm = cm;
-  sw.row_off = row_off; sw.nrows = nrows;
+// transposed op (no bias) of type SEG_WBWD / SEG_WBWD3 / SEG_WBWD3H: KT tiles over the layer's input space, reduction over its output rows in KC chunks
+void emit_dense_bwd(Builder& b, const NetPlan& np, int l, int type, int KT, int KC, ColMap cm, int row_off, int nrows, float mult = 1.0f) {
+  Seg sw = base_seg(np, l, type);
+  sw.NT = KT; sw.KC = KC; sw.used = KT * KC * (type == SEG_WBWD ? 1 : 3); sw.cm = cm; sw.mult = mult; sw.row_off = row_off; sw.nrows = nrows;
+  sw.nchunks = type == SEG_WBWD ? bwd_op_chunks(KT, KC) : type == SEG_WBWD3 ? x3_bwd_chunks(KT, KC) : x3h_bwd_chunks(KT, KC);
   b.add(sw);
 }
-// bf16x3 forward op (x3.h): [NT*4 bias chunks][KC16 * NT * 3 split-plane chunks] padded to stages
-void emit_dense_fwd3(Builder& b, const NetPlan& np, int l, int NT, int KC16, ColMap cm, float mult) {
-  Seg sb = base_seg(np, l, SEG_BIAS);
-  sb.NT = NT; sb.KC = 4; sb.nchunks = NT * 4; sb.used = NT * 4;
-  b.add(sb);
-  Seg sw = base_seg(np, l, SEG_WFWD3);
-  sw.NT = NT; sw.KC = KC16; sw.used = KC16 * NT * 3; sw.nchunks = x3_op_chunks(NT, KC16) - NT * 4; sw.cm = cm; sw.mult = mult;
-  b.add(sw);
-}
-// transposed bf16x3 op (no bias): KT tiles over the layer's input space, reduction over its output rows in 16-chunks
-void emit_dense_bwd3(Builder& b, const NetPlan& np, int l, int KT, int KC16, ColMap cm, int row_off, int nrows, float mult) {
-  Seg sw = base_seg(np, l, SEG_WBWD3);
-  sw.NT = KT; sw.KC = KC16; sw.used = KC16 * KT * 3; sw.nchunks = round_up(KC16 * KT * 3, SC); sw.cm = cm; sw.mult = mult;
-  sw.row_off = row_off; sw.nrows = nrows;
-  b.add(sw);
-}
-// 16-point-wave family (x3h.h): [NT bias chunks][KC32 * NT * 3 split-plane chunks] padded to stages; NT = 16-row tiles
-void emit_dense_fwd3h(Builder& b, const NetPlan& np, int l, int NT, int KC32, ColMap cm, float mult, int row_off, int nrows) {
-  Seg sb = base_seg(np, l, SEG_BIAS_H);
-  sb.NT = NT; sb.KC = 1; sb.nchunks = NT; sb.used = NT; sb.row_off = row_off; sb.nrows = nrows;
-  b.add(sb);
-  Seg sw = base_seg(np, l, SEG_WFWD3H);
-  sw.NT = NT; sw.KC = KC32; sw.used = KC32 * NT * 3; sw.nchunks = x3h_op_chunks(NT, KC32) - NT; sw.cm = cm; sw.mult = mult;
-  sw.row_off = row_off; sw.nrows = nrows;
-  b.add(sw);
-}
-// the same op with the two leading split planes only (x3h.h: dense_x3h<..., PL = 2>)
-void emit_dense_fwd2h(Builder& b, const NetPlan& np, int l, int NT, int KC32, ColMap cm, float mult, int row_off, int nrows) {
-  Seg sb = base_seg(np, l, SEG_BIAS_H);
-  sb.NT = NT; sb.KC = 1; sb.nchunks = NT; sb.used = NT; sb.row_off = row_off; sb.nrows = nrows;
-  b.add(sb);
-  Seg sw = base_seg(np, l, SEG_WFWD2H);
-  sw.NT = NT; sw.KC = KC32; sw.used = KC32 * NT * 2; sw.nchunks = x3h_op_chunks(NT, KC32, 2) - NT; sw.cm = cm; sw.mult = mult;
-  sw.row_off = row_off; sw.nrows = nrows;
-  b.add(sw);
-}
-void emit_dense_bwd3h(Builder& b, const NetPlan& np, int l, int KT, int KC32, ColMap cm, int row_off, int nrows, float mult) {
-  Seg sw = base_seg(np, l, SEG_WBWD3H);
-  sw.NT = KT; sw.KC = KC32; sw.used = KC32 * KT * 3; sw.nchunks = x3h_bwd_chunks(KT, KC32); sw.cm = cm; sw.mult = mult;
-  sw.row_off = row_off; sw.nrows = nrows;
-  b.add(sw);
-}
-void emit_rowvec_h(Builder& b, const NetPlan& np, int l, int nrows, int NTK, ColMap cm) {
-  Seg sw = base_seg(np, l, SEG_ROWVEC_H);
-  sw.NT = nrows; sw.KC = NTK; sw.used = nrows * NTK; sw.nchunks = nrows * NTK; sw.cm = cm; sw.nrows = nrows;
+// the first nrows rows of layer l as row vectors over the net's hidden width, then one scalar chunk
+void emit_rowvec(Builder& b, const NetPlan& np, int l, const Family& f, int nrows) {
+  const int KC = np.d.hidden / f.rv_width;
+  Seg sw = base_seg(np, l, f.rowvec_type);
+  sw.NT = nrows; sw.KC = KC; sw.used = nrows * KC; sw.nchunks = nrows * KC; sw.cm = cols(np.d.hidden); sw.nrows = nrows;
   b.add(sw);
   Seg sc = base_seg(np, l, SEG_SCALAR);
-  sc.nchunks = rowvec_h_chunks(NTK, nrows) - nrows * NTK; sc.used = 1; sc.nrows = nrows;
+  sc.nchunks = (f.rowvec_type == SEG_ROWVEC ? rowvec_chunks(KC, nrows) : rowvec_h_chunks(KC, nrows)) - nrows * KC; sc.used = 1; sc.nrows = nrows;
   b.add(sc);
 }
-void emit_rowvec(Builder& b, const NetPlan& np, int l, int nrows, int KC, ColMap cm) {
-  Seg sw = base_seg(np, l, SEG_ROWVEC);
-  sw.NT = nrows; sw.KC = KC; sw.used = nrows * KC; sw.nchunks = nrows * KC; sw.cm = cm; sw.nrows = nrows;
-  b.add(sw);
-  Seg sc = base_seg(np, l, SEG_SCALAR);
-  sc.nchunks = rowvec_chunks(KC, nrows) - nrows * KC; sc.used = 1; sc.nrows = nrows;
-  b.add(sc);
+// the hidden layers of the SDF net, bottom-up: layer 0 reduces over PE(x), the skip layer over [h | PE(x)] (both parts padded to k-chunks)
+void emit_sdf_hidden(Builder& b, const NetPlan& np, const Family& f) {
+  const i2sdf_mlp_desc& d = np.d;
+  const int H = d.hidden, PED = pe_dim(d), PEK = cdiv(PED, f.k_width);
+  for (int l = 0; l < d.n_lin - 1; ++l) {
+    ColMap cm = cols(d.in_dim[l]);
+    int KC = (l == 0) ? PEK : H / f.k_width;
+    float mult = 1.0f;
+    if (l == d.skip_layer) {
+      cm = ColMap{H, 0, d.in_dim[l] - PED, d.in_dim[l] - PED, PED}; KC += PEK;
+      if (f.fold_skip) mult = RS2;
+    }
+    emit_dense(b, np, l, f, H / f.tile_rows, KC, cm, mult, 0, d.out_dim[l]);
+  }
 }
 
 int check_mlp(const i2sdf_mlp_desc& d) {
   if (d.n_lin < 2 || d.n_lin > I2SDF_MAX_LAYERS) return I2SDF_EINVAL;
   if (d.hidden % 32 || d.hidden < 32 || d.hidden > 256) return I2SDF_EINVAL;
   return I2SDF_OK;
+}
+
+// records the builder's cursor under every mark of `ms` (a stream the shape has no kernels for keeps all its marks on one position)
+void mark_here(NetPlan& np, const Builder& b, std::initializer_list<Mark> ms) {
+  for (Mark k : ms) np.mark[k] = b.chunk;
 }
 
 // ---- SDF net (ImplicitNetwork with positional encoding) -------------------------------------
@@ -157,99 +148,76 @@ int build_sdf(i2sdf_plan* p, Builder& b) {
   }
   if (d.in_dim[L - 1] != H) return I2SDF_EINVAL;
   p->H = H; p->F = F;
-  // forward stream
-  np.fwd_chunk0 = b.chunk;
-  for (int l = 0; l < L - 1; ++l) {
-    ColMap cm{HUGE_SPLIT, 0, d.in_dim[l], 0, 0};
-    int KC = (l == 0) ? PEC : H / 8;
-    if (l == d.skip_layer) { cm = ColMap{H, 0, d.in_dim[l] - PED, d.in_dim[l] - PED, PED}; KC += PEC; }
-    emit_dense_fwd(b, np, l, H / 32, KC, cm, 0, d.out_dim[l]);
-  }
-  emit_rowvec(b, np, L - 1, 1, H / 8, ColMap{HUGE_SPLIT, 0, H, 0, 0});
-  if (F > 0) emit_dense_fwd(b, np, L - 1, F / 32, H / 8, ColMap{HUGE_SPLIT, 0, H, 0, 0}, 1, F);
-  np.fwd_chunks = b.chunk - np.fwd_chunk0;
+  const bool even_tiles = (H / 32) % 2 == 0, wide = H == 256 && F == 256;      // shapes the bf16x3 kernels of x3.h / x3h.h are built for
+  const int PT = cdiv(PEC * 8, 32);                                            // 32-row tiles of the padded PE space
+  // forward stream: hidden layers, sdf row, feature rows
+  mark_here(np, b, {FWD});
+  emit_sdf_hidden(b, np, FP32);
+  mark_here(np, b, {FWD_HIDDEN_END});
+  emit_rowvec(b, np, L - 1, FP32, 1);
+  mark_here(np, b, {FWD_SDF_END});
+  if (F > 0) emit_dense(b, np, L - 1, FP32, F / 32, H / 8, cols(H), 1.0f, 1, F);
+  mark_here(np, b, {FWD_END});
   // reverse (transposed) stream: [w_sdf][Wfeat^T][w_sdf][W_{L-2}^T] ... [W_0^T]
-  //   backward sweep 2 starts at rev_chunk0 (needs w_sdf before the feature op so that the op's epilogue can use it) and
-  //   skips the second copy; the d sdf/dx chain starts at rev_wsdf_chunk.
-  np.rev_chunk0 = b.chunk;
-  emit_rowvec(b, np, L - 1, 1, H / 8, ColMap{HUGE_SPLIT, 0, H, 0, 0});
-  if (F > 0) emit_dense_bwd(b, np, L - 1, H / 32, F / 8, ColMap{HUGE_SPLIT, 0, H, 0, 0}, 1, F);
-  np.rev_wsdf_chunk = b.chunk;
-  emit_rowvec(b, np, L - 1, 1, H / 8, ColMap{HUGE_SPLIT, 0, H, 0, 0});
+  //   backward sweep 2 starts at REV (needs w_sdf before the feature op so that the op's epilogue can use it), skips the
+  //   second copy and stops in front of W_0^T; the d sdf/dx chain starts at REV_CHAIN.
+  mark_here(np, b, {REV});
+  emit_rowvec(b, np, L - 1, FP32, 1);
+  if (F > 0) emit_dense_bwd(b, np, L - 1, SEG_WBWD, H / 32, F / 8, cols(H), 1, F);
+  mark_here(np, b, {REV_CHAIN});
+  emit_rowvec(b, np, L - 1, FP32, 1);
   for (int l = L - 2; l >= 0; --l) {
-    ColMap cm{HUGE_SPLIT, 0, d.in_dim[l], 0, 0};
-    int KT = (l == 0) ? cdiv(PEC * 8, 32) : H / 32;
-    if (l == d.skip_layer) { cm = ColMap{H, 0, d.in_dim[l] - PED, d.in_dim[l] - PED, PED}; KT += cdiv(PEC * 8, 32); }
-    emit_dense_bwd(b, np, l, KT, H / 8, cm, 0, d.out_dim[l]);
+    ColMap cm = cols(d.in_dim[l]);
+    int KT = (l == 0) ? PT : H / 32;
+    if (l == d.skip_layer) { cm = ColMap{H, 0, d.in_dim[l] - PED, d.in_dim[l] - PED, PED}; KT += PT; }
+    if (l == 0) mark_here(np, b, {REV_W0});
+    emit_dense_bwd(b, np, l, SEG_WBWD, KT, H / 8, cm, 0, d.out_dim[l]);
   }
-  np.rev_chunks = b.chunk - np.rev_chunk0;
-  // bf16x3 forward stream (sampler / grid queries without features): hidden layers K-outer, then the fp32 sdf row.
-  // The 1/sqrt(2) of the skip concatenation is folded into that layer's weights.
-  np.fwd3_chunk0 = b.chunk;
-  if ((H / 32) % 2 == 0) {
-    const int PE16 = cdiv(PED, 16);
-    for (int l = 0; l < L - 1; ++l) {
-      ColMap cm{HUGE_SPLIT, 0, d.in_dim[l], 0, 0};
-      int KC16 = (l == 0) ? PE16 : H / 16;
-      float mult = 1.0f;
-      if (l == d.skip_layer) { cm = ColMap{H, 0, d.in_dim[l] - PED, d.in_dim[l] - PED, PED}; KC16 += PE16; mult = 0.70710678118654752440f; }
-      emit_dense_fwd3(b, np, l, H / 32, KC16, cm, mult);
-    }
-    emit_rowvec(b, np, L - 1, 1, H / 8, ColMap{HUGE_SPLIT, 0, H, 0, 0});
+  mark_here(np, b, {REV_END});
+  // bf16x3 forward stream (backward sweep 1; sdf-only queries of 64-wide nets): hidden layers K-outer, then the fp32 sdf row
+  mark_here(np, b, {FWD3, FWD3_HIDDEN_END, FWD3_END});
+  if (even_tiles) {
+    emit_sdf_hidden(b, np, X3);
+    mark_here(np, b, {FWD3_HIDDEN_END});
+    emit_rowvec(b, np, L - 1, X3, 1);
+    mark_here(np, b, {FWD3_END});
   }
-  np.fwd3_chunks = b.chunk - np.fwd3_chunk0;
-  // bf16x3 reverse stream (d sdf/dx chain): [w_sdf row][W_{L-2}^T] ... [W_0^T]; skip factor folded into the weights
-  np.rev3_chunk0 = b.chunk;
-  if ((H / 32) % 2 == 0) {
-    const int PT = cdiv(PEC * 8, 32);
-    // backward sweep 2 starts here: [w_sdf][W_feat^T]; the d sdf/dx chain starts at rev3_wsdf_chunk: [w_sdf][W_{L-2}^T]...
-    emit_rowvec(b, np, L - 1, 1, H / 8, ColMap{HUGE_SPLIT, 0, H, 0, 0});
-    if (F > 0 && F % 16 == 0) emit_dense_bwd3(b, np, L - 1, H / 32, F / 16, ColMap{HUGE_SPLIT, 0, H, 0, 0}, 1, F, 1.0f);
-    np.rev3_wsdf_chunk = b.chunk;
-    emit_rowvec(b, np, L - 1, 1, H / 8, ColMap{HUGE_SPLIT, 0, H, 0, 0});
+  // bf16x3 reverse stream, laid out as the fp32 one; skip factor folded into the weights
+  mark_here(np, b, {REV3, REV3_CHAIN, REV3_W0, REV3_END});
+  if (even_tiles) {
+    emit_rowvec(b, np, L - 1, X3, 1);
+    if (F > 0 && F % 16 == 0) emit_dense_bwd(b, np, L - 1, SEG_WBWD3, H / 32, F / 16, cols(H), 1, F);
+    mark_here(np, b, {REV3_CHAIN});
+    emit_rowvec(b, np, L - 1, X3, 1);
     for (int l = L - 2; l >= 0; --l) {
+      if (l == 0) mark_here(np, b, {REV3_W0});
       // the skip layer's transposed op is emitted as two ops over the same reduction: hidden part, then PE part
       if (l == d.skip_layer) {
-        const float rs2 = 0.70710678118654752440f;
-        emit_dense_bwd3(b, np, l, H / 32, H / 16, ColMap{HUGE_SPLIT, 0, d.in_dim[l] - PED, 0, 0}, 0, d.out_dim[l], rs2);
-        emit_dense_bwd3(b, np, l, PT, H / 16, ColMap{HUGE_SPLIT, d.in_dim[l] - PED, PED, 0, 0}, 0, d.out_dim[l], rs2);
+        emit_dense_bwd(b, np, l, SEG_WBWD3, H / 32, H / 16, cols(d.in_dim[l] - PED), 0, d.out_dim[l], RS2);
+        emit_dense_bwd(b, np, l, SEG_WBWD3, PT, H / 16, ColMap{HUGE_SPLIT, d.in_dim[l] - PED, PED, 0, 0}, 0, d.out_dim[l], RS2);
       } else {
-        emit_dense_bwd3(b, np, l, (l == 0) ? PT : H / 32, H / 16, ColMap{HUGE_SPLIT, 0, d.in_dim[l], 0, 0}, 0, d.out_dim[l], 1.0f);
+        emit_dense_bwd(b, np, l, SEG_WBWD3, (l == 0) ? PT : H / 32, H / 16, cols(d.in_dim[l]), 0, d.out_dim[l]);
       }
     }
+    mark_here(np, b, {REV3_END});
   }
-  np.rev3_chunks = b.chunk - np.rev3_chunk0;
-  // the same two streams for the 16-point-wave kernels (x3h.h): 16-row tiles, 32-wide k-chunks, same ops in the same order
-  np.fwd3h_chunk0 = b.chunk;
-  if (H == 256 && F == 256) {
-    const int PE32 = cdiv(PED, 32);
-    for (int l = 0; l < L - 1; ++l) {
-      ColMap cm{HUGE_SPLIT, 0, d.in_dim[l], 0, 0};
-      int KC32 = (l == 0) ? PE32 : H / 32;
-      float mult = 1.0f;
-      if (l == d.skip_layer) { cm = ColMap{H, 0, d.in_dim[l] - PED, d.in_dim[l] - PED, PED}; KC32 += PE32; mult = 0.70710678118654752440f; }
-      emit_dense_fwd3h(b, np, l, H / 16, KC32, cm, mult, 0, d.out_dim[l]);
-    }
-    emit_rowvec_h(b, np, L - 1, 1, H / 16, ColMap{HUGE_SPLIT, 0, H, 0, 0});
-    emit_dense_fwd3h(b, np, L - 1, F / 16, H / 32, ColMap{HUGE_SPLIT, 0, H, 0, 0}, 1.0f, 1, F);          // feature rows
+  // the forward stream for the 16-point-wave kernels (x3h.h): same ops in the same order, with the feature rows.  (No reverse stream of this
+  // family for the SDF net: its d sdf/dx chain and sweeps run on 32-point waves.)
+  mark_here(np, b, {FWD3H, FWD3H_SDF_END, FWD3H_END});
+  if (wide) {
+    emit_sdf_hidden(b, np, X3H);
+    emit_rowvec(b, np, L - 1, X3H, 1);
+    mark_here(np, b, {FWD3H_SDF_END});
+    emit_dense(b, np, L - 1, X3H, F / 16, H / 32, cols(H), 1.0f, 1, F);          // feature rows
+    mark_here(np, b, {FWD3H_END});
   }
-  np.fwd3h_chunks = b.chunk - np.fwd3h_chunk0;
-  np.rev3h_chunk0 = b.chunk;          // (no reverse stream of this family for the SDF net: its d sdf/dx chain and sweeps run on 32-point waves)
-  np.rev3h_chunks = b.chunk - np.rev3h_chunk0;
   // the sampler's passes with two split planes (I2SDF_OPT_SAMPLER_BF16X2): hidden layers + the fp32 sdf row, 2/3 of the bytes and stages
-  np.fwd2h_chunk0 = b.chunk;
-  if (H == 256 && F == 256) {
-    const int PE32 = cdiv(PED, 32);
-    for (int l = 0; l < L - 1; ++l) {
-      ColMap cm{HUGE_SPLIT, 0, d.in_dim[l], 0, 0};
-      int KC32 = (l == 0) ? PE32 : H / 32;
-      float mult = 1.0f;
-      if (l == d.skip_layer) { cm = ColMap{H, 0, d.in_dim[l] - PED, d.in_dim[l] - PED, PED}; KC32 += PE32; mult = 0.70710678118654752440f; }
-      emit_dense_fwd2h(b, np, l, H / 16, KC32, cm, mult, 0, d.out_dim[l]);
-    }
-    emit_rowvec_h(b, np, L - 1, 1, H / 16, ColMap{HUGE_SPLIT, 0, H, 0, 0});
+  mark_here(np, b, {FWD2H, FWD2H_END});
+  if (wide) {
+    emit_sdf_hidden(b, np, X2H);
+    emit_rowvec(b, np, L - 1, X2H, 1);
+    mark_here(np, b, {FWD2H_END});
   }
-  np.fwd2h_chunks = b.chunk - np.fwd2h_chunk0;
   return I2SDF_OK;
 }
 
@@ -262,33 +230,29 @@ int build_rgb(i2sdf_plan* p, Builder& b) {
   if (d.skip_layer >= 0 || d.d_out != 3 || d.multires <= 0 || d.in0 != PED + F || F <= 0) return I2SDF_EINVAL;
   for (int l = 0; l < L - 1; ++l)
     if (d.out_dim[l] != H || d.in_dim[l] != (l == 0 ? PED + F : H)) return I2SDF_EINVAL;
-  np.fwd_chunk0 = b.chunk;
-  emit_dense_fwd(b, np, 0, H / 32, PEC + F / 8, ColMap{PEC * 8, 0, PED, PED, F}, 0, H);
-  for (int l = 1; l < L - 1; ++l) emit_dense_fwd(b, np, l, H / 32, H / 8, ColMap{HUGE_SPLIT, 0, H, 0, 0}, 0, H);
-  emit_rowvec(b, np, L - 1, 3, H / 8, ColMap{HUGE_SPLIT, 0, H, 0, 0});
-  np.fwd_chunks = b.chunk - np.fwd_chunk0;
-  np.rev_chunk0 = b.chunk;
-  emit_rowvec(b, np, L - 1, 3, H / 8, ColMap{HUGE_SPLIT, 0, H, 0, 0});
-  for (int l = L - 2; l >= 1; --l) emit_dense_bwd(b, np, l, H / 32, H / 8, ColMap{HUGE_SPLIT, 0, H, 0, 0}, 0, H);
-  emit_dense_bwd(b, np, 0, F / 32, H / 8, ColMap{HUGE_SPLIT, PED, F, 0, 0}, 0, H);   // feature columns only
-  np.rev_chunks = b.chunk - np.rev_chunk0;
-  np.fwd3_chunk0 = np.rev3_chunk0 = b.chunk;      // (the radiance net's bf16x3 kernels all run on 16-point waves)
+  const bool wide = H == 256 && F == 256 && L >= 3;      // (the radiance net's bf16x3 kernels all run on 16-point waves)
+  mark_here(np, b, {FWD});
+  emit_dense(b, np, 0, FP32, H / 32, PEC + F / 8, ColMap{PEC * 8, 0, PED, PED, F}, 1.0f, 0, H);
+  for (int l = 1; l < L - 1; ++l) emit_dense(b, np, l, FP32, H / 32, H / 8, cols(H), 1.0f, 0, H);
+  emit_rowvec(b, np, L - 1, FP32, 3);
+  mark_here(np, b, {FWD_END, REV});
+  emit_rowvec(b, np, L - 1, FP32, 3);
+  for (int l = L - 2; l >= 1; --l) emit_dense_bwd(b, np, l, SEG_WBWD, H / 32, H / 8, cols(H), 0, H);
+  emit_dense_bwd(b, np, 0, SEG_WBWD, F / 32, H / 8, ColMap{HUGE_SPLIT, PED, F, 0, 0}, 0, H);   // feature columns only
+  mark_here(np, b, {REV_END});
   // bf16x3 streams, 16-point-wave family (x3h.h): layer 0 reduces over [PE(view) padded to 32-chunks | feature]
-  np.fwd3h_chunk0 = b.chunk;
-  if (H == 256 && F == 256 && L >= 3) {
+  mark_here(np, b, {FWD3H, FWD3H_END, REV3H, REV3H_END});
+  if (wide) {
     const int PV32 = cdiv(PED, 32);
-    emit_dense_fwd3h(b, np, 0, H / 16, PV32 + F / 32, ColMap{PV32 * 32, 0, PED, PED, F}, 1.0f, 0, H);
-    for (int l = 1; l < L - 1; ++l) emit_dense_fwd3h(b, np, l, H / 16, H / 32, ColMap{HUGE_SPLIT, 0, H, 0, 0}, 1.0f, 0, H);
-    emit_rowvec_h(b, np, L - 1, 3, H / 16, ColMap{HUGE_SPLIT, 0, H, 0, 0});
+    emit_dense(b, np, 0, X3H, H / 16, PV32 + F / 32, ColMap{PV32 * 32, 0, PED, PED, F}, 1.0f, 0, H);
+    for (int l = 1; l < L - 1; ++l) emit_dense(b, np, l, X3H, H / 16, H / 32, cols(H), 1.0f, 0, H);
+    emit_rowvec(b, np, L - 1, X3H, 3);
+    mark_here(np, b, {FWD3H_END, REV3H});
+    emit_rowvec(b, np, L - 1, X3H, 3);
+    for (int l = L - 2; l >= 1; --l) emit_dense_bwd(b, np, l, SEG_WBWD3H, H / 16, H / 32, cols(H), 0, H);
+    emit_dense_bwd(b, np, 0, SEG_WBWD3H, F / 16, H / 32, ColMap{HUGE_SPLIT, PED, F, 0, 0}, 0, H);
+    mark_here(np, b, {REV3H_END});
   }
-  np.fwd3h_chunks = b.chunk - np.fwd3h_chunk0;
-  np.rev3h_chunk0 = b.chunk;
-  if (H == 256 && F == 256 && L >= 3) {
-    emit_rowvec_h(b, np, L - 1, 3, H / 16, ColMap{HUGE_SPLIT, 0, H, 0, 0});
-    for (int l = L - 2; l >= 1; --l) emit_dense_bwd3h(b, np, l, H / 16, H / 32, ColMap{HUGE_SPLIT, 0, H, 0, 0}, 0, H, 1.0f);
-    emit_dense_bwd3h(b, np, 0, F / 16, H / 32, ColMap{HUGE_SPLIT, PED, F, 0, 0}, 0, H, 1.0f);
-  }
-  np.rev3h_chunks = b.chunk - np.rev3h_chunk0;
   return I2SDF_OK;
 }
 
@@ -300,20 +264,19 @@ int build_light(i2sdf_plan* p, Builder& b) {
   const int H = d.hidden, F = p->F;
   if (d.n_lin != 2 || H % 32 || H > 256 || d.d_out != 1 || d.in0 != F || d.multires != 0) return I2SDF_EINVAL;
   if (d.out_dim[0] != H || d.in_dim[0] != F || d.in_dim[1] != H) return I2SDF_EINVAL;
-  np.fwd_chunk0 = b.chunk;
-  emit_dense_fwd(b, np, 0, H / 32, F / 8, ColMap{HUGE_SPLIT, 0, F, 0, 0}, 0, H);
-  emit_rowvec(b, np, 1, 1, H / 8, ColMap{HUGE_SPLIT, 0, H, 0, 0});
-  np.fwd_chunks = b.chunk - np.fwd_chunk0;
-  np.rev_chunk0 = b.chunk;
-  emit_rowvec(b, np, 1, 1, H / 8, ColMap{HUGE_SPLIT, 0, H, 0, 0});
-  np.rev_chunks = b.chunk - np.rev_chunk0;
+  mark_here(np, b, {FWD});
+  emit_dense(b, np, 0, FP32, H / 32, F / 8, cols(F), 1.0f, 0, H);
+  emit_rowvec(b, np, 1, FP32, 1);
+  mark_here(np, b, {FWD_END, REV});
+  emit_rowvec(b, np, 1, FP32, 1);
+  mark_here(np, b, {REV_END});
   // the forward on 16-point waves (mlp_x3h.hip: light_fwd3h_kernel), shapes of the shipped config only
-  np.fwd3h_chunk0 = b.chunk;
+  mark_here(np, b, {FWD3H, FWD3H_END});
   if (H == 128 && F == 256) {
-    emit_dense_fwd3h(b, np, 0, H / 16, F / 32, ColMap{HUGE_SPLIT, 0, F, 0, 0}, 1.0f, 0, H);
-    emit_rowvec_h(b, np, 1, 1, H / 16, ColMap{HUGE_SPLIT, 0, H, 0, 0});
+    emit_dense(b, np, 0, X3H, H / 16, F / 32, cols(F), 1.0f, 0, H);
+    emit_rowvec(b, np, 1, X3H, 1);
+    mark_here(np, b, {FWD3H_END});
   }
-  np.fwd3h_chunks = b.chunk - np.fwd3h_chunk0;
   return I2SDF_OK;
 }
 
@@ -548,7 +511,7 @@ extern "C" int i2sdf_plan_set_option(i2sdf_plan* p, int32_t option, int32_t valu
   if (option == I2SDF_OPT_SDF_FWD_BF16X3) {
     // the option is accepted only where a bf16x3 kernel will actually run (mlp_fwd.hip: launch_sdf_fwd): 256-wide nets on the 16-point-wave
     // stream, 64-wide nets on the 32-point stream -- a shape with neither would otherwise report success and fall through to fp32 MFMA
-    const bool runs = (p->H == 256 && p->F == 256 && p->sdf.fwd3h_chunks > 0) || (p->H == 64 && p->F == 64 && p->sdf.fwd3_chunks > 0);
+    const bool runs = (p->H == 256 && p->F == 256 && span_chunks(p->sdf, SPAN_FWD3H) > 0) || (p->H == 64 && p->F == 64 && span_chunks(p->sdf, SPAN_FWD3) > 0);
     if (value && !runs) return I2SDF_EINVAL;
     p->sdf_fwd_bf16x3 = value ? 1 : 0;
     return I2SDF_OK;
@@ -556,22 +519,22 @@ extern "C" int i2sdf_plan_set_option(i2sdf_plan* p, int32_t option, int32_t valu
   if (option == I2SDF_OPT_SAMPLER_BF16X2) {
     // only the passes inside i2sdf_sample_rays / i2sdf_render_image (they choose depths); i2sdf_sdf_forward and i2sdf_sdf_grid return values
     // and keep three planes.  Needs the 16-point-wave forward (I2SDF_OPT_SDF_FWD_BF16X3 on a 256-wide net).
-    if (value && (p->sdf.fwd2h_chunks == 0 || p->H != 256 || p->F != 256)) return I2SDF_EINVAL;
+    if (value && (span_chunks(p->sdf, SPAN_FWD2H) == 0 || p->H != 256 || p->F != 256)) return I2SDF_EINVAL;
     p->sampler_bf16x2 = value ? 1 : 0;
     return I2SDF_OK;
   }
   if (option == I2SDF_OPT_TRAIN_FWD_BF16X3) {
-    if (value && (p->sdf.rev3_chunks == 0 || p->sdf.fwd3h_chunks == 0 || p->H != 256 || p->F != 256)) return I2SDF_EINVAL;
+    if (value && (span_chunks(p->sdf, SPAN_REV3_CHAIN) == 0 || span_chunks(p->sdf, SPAN_FWD3H) == 0 || p->H != 256 || p->F != 256)) return I2SDF_EINVAL;
     p->train_fwd_bf16x3 = value ? 1 : 0;
     return I2SDF_OK;
   }
   if (option == I2SDF_OPT_SDF_BWD_BF16X3) {
-    if (value && (p->sdf.rev3_chunks == 0 || p->H != 256 || p->F != 256)) return I2SDF_EINVAL;
+    if (value && (span_chunks(p->sdf, SPAN_REV3_CHAIN) == 0 || p->H != 256 || p->F != 256)) return I2SDF_EINVAL;
     p->sdf_bwd_bf16x3 = value ? 1 : 0;
     return I2SDF_OK;
   }
   if (option == I2SDF_OPT_RGB_BF16X3) {
-    if (value && (p->rgb.rev3h_chunks == 0 || p->rgb.d.hidden != 256 || p->F != 256 || p->rgb.d.n_lin < 3)) return I2SDF_EINVAL;
+    if (value && (span_chunks(p->rgb, SPAN_REV3H) == 0 || p->rgb.d.hidden != 256 || p->F != 256 || p->rgb.d.n_lin < 3)) return I2SDF_EINVAL;
     p->rgb_bf16x3 = value ? 1 : 0;
     return I2SDF_OK;
   }
@@ -588,7 +551,7 @@ extern "C" int i2sdf_plan_set_option(i2sdf_plan* p, int32_t option, int32_t valu
     return I2SDF_OK;
   }
   if (option == I2SDF_OPT_SAVES24) {
-    if (value && (p->H != 256 || p->F != 256 || p->sdf.rev3_chunks == 0)) return I2SDF_EINVAL;
+    if (value && (p->H != 256 || p->F != 256 || span_chunks(p->sdf, SPAN_REV3_CHAIN) == 0)) return I2SDF_EINVAL;
     if (p->chain_active) return I2SDF_EINVAL;          // the layout of tensors in flight
     p->saves24 = value ? 1 : 0;
     return I2SDF_OK;

@@ -1,6 +1,8 @@
 // Host-side plan: where every packed weight stream lives and how it is produced from the flat parameter
 // buffer.  The kernels walk the streams linearly; the order of ops inside a stream is fixed by the
-// kernel's own static structure (see mlp_fwd.hip), and build_*_stream() below must emit the same order.
+// kernel's own static structure (see mlp_fwd.hip), and build_sdf / build_rgb / build_light (plan.cpp) emit the same order.
+// plan.cpp is the only place that knows the layout: while it emits a stream it records the positions a launch takes as
+// marks, and a launch site turns two marks into (pointer, stage count) with i2sdf::span().
 #pragma once
 #include <stdint.h>
 #include <vector>
@@ -36,23 +38,39 @@ struct Seg {
   float mult;
 };
 
-struct LayerGeom {       // per net, per layer: padded geometry shared by pack + kernels
-  int32_t NT;            // output tiles (32 rows each)
-  int32_t KC;            // input chunks (8 cols each)
+// Positions inside a net's streams (chunk index in the pack buffer), recorded by plan.cpp while it emits them.  A stream the net's
+// shape has no kernels for is empty: all its marks coincide.
+enum Mark : int {
+  FWD, FWD_HIDDEN_END, FWD_SDF_END, FWD_END,      // fp32 forward: hidden layers | output row vector(s) | feature rows (sdf net)
+  REV, REV_CHAIN, REV_W0, REV_END,                // fp32 reverse, sdf net: [w_sdf][W_feat^T] | [w_sdf][W_{L-2}^T .. W_1^T] | [W_0^T]
+  FWD3, FWD3_HIDDEN_END, FWD3_END,                // bf16x3 forward, 32-point waves (x3.h): hidden layers | sdf row
+  REV3, REV3_CHAIN, REV3_W0, REV3_END,            // bf16x3 reverse, as REV (the skip layer's transposed op is two ops: hidden part, PE part)
+  FWD3H, FWD3H_SDF_END, FWD3H_END,                // bf16x3 forward, 16-point waves (x3h.h): hidden layers, output row vector(s) | feature rows
+  REV3H, REV3H_END,                               // bf16x3 reverse, 16-point waves (radiance net)
+  FWD2H, FWD2H_END,                               // sdf net, hidden layers + sdf row with TWO split planes (I2SDF_OPT_SAMPLER_BF16X2)
+  N_MARKS
 };
+// What a launch walks: from one mark to another, in LDS stages of `stage_chunks` chunks (SC: 32-point waves, SCH: 16-point waves).
+struct SpanId { Mark from, to; int stage_chunks; };
+constexpr SpanId SPAN_FWD_HIDDEN{FWD, FWD_HIDDEN_END, SC};        // backward sweep 1
+constexpr SpanId SPAN_FWD_SDF{FWD, FWD_SDF_END, SC};              // sdf-only forward
+constexpr SpanId SPAN_FWD{FWD, FWD_END, SC};
+constexpr SpanId SPAN_REV_SWEEP2{REV, REV_W0, SC};                // backward sweep 2 stops in front of W_0^T: the points carry no gradient
+constexpr SpanId SPAN_REV_CHAIN{REV_CHAIN, REV_END, SC};          // the d sdf/dx chain starts at the second w_sdf
+constexpr SpanId SPAN_REV{REV, REV_END, SC};                      // radiance net, light head: the whole stream
+constexpr SpanId SPAN_FWD3_HIDDEN{FWD3, FWD3_HIDDEN_END, SC};
+constexpr SpanId SPAN_FWD3{FWD3, FWD3_END, SC};
+constexpr SpanId SPAN_REV3_SWEEP2{REV3, REV3_W0, SC};
+constexpr SpanId SPAN_REV3_CHAIN{REV3_CHAIN, REV3_END, SC};
+constexpr SpanId SPAN_FWD3H_SDF{FWD3H, FWD3H_SDF_END, SCH};
+constexpr SpanId SPAN_FWD3H{FWD3H, FWD3H_END, SCH};
+constexpr SpanId SPAN_REV3H{REV3H, REV3H_END, SCH};
+constexpr SpanId SPAN_FWD2H{FWD2H, FWD2H_END, SCH};
 
 struct NetPlan {
   i2sdf_mlp_desc d;
   int32_t scale_off[I2SDF_MAX_LAYERS];
-  int64_t fwd_chunk0 = 0, fwd_chunks = 0;      // forward stream
-  int64_t rev_chunk0 = 0, rev_chunks = 0;      // transposed / reverse stream
-  int64_t rev_wsdf_chunk = 0;                  // where the igrad chain starts inside rev (sdf net)
-  int64_t fwd3_chunk0 = 0, fwd3_chunks = 0;    // bf16x3 forward stream: hidden layers, sdf row, feature rows (sdf net, x3.h)
-  int64_t rev3_chunk0 = 0, rev3_chunks = 0;    // bf16x3 reverse stream: [w_sdf][W_feat^T][w_sdf][W_{L-2}^T] ... [W_0^T]
-  int64_t rev3_wsdf_chunk = 0;                 // where the d sdf/dx chain starts inside it
-  int64_t fwd3h_chunk0 = 0, fwd3h_chunks = 0;  // bf16x3 streams of the 16-point-wave kernels (x3h.h): sdf net forward [hidden layers, sdf row, feature rows];
-  int64_t rev3h_chunk0 = 0, rev3h_chunks = 0;  // radiance net forward and reverse
-  int64_t fwd2h_chunk0 = 0, fwd2h_chunks = 0;  // sdf net, hidden layers + sdf row with TWO split planes (I2SDF_OPT_SAMPLER_BF16X2)
+  int64_t mark[N_MARKS] = {};
   int64_t wgrad_off[I2SDF_MAX_LAYERS];         // offset (floats) of layer l's [rowsP x colsP] block in the wgrad buffer
   int32_t wg_rows[I2SDF_MAX_LAYERS], wg_cols[I2SDF_MAX_LAYERS];   // padded shape of that block
 };
@@ -93,6 +111,20 @@ struct i2sdf_plan {
   mutable int32_t chain_active = 0;          // between i2sdf_chain_begin and i2sdf_chain_end
   mutable int64_t chain_M = 0;               // the point count the active chain's ranges were cut from
 };
+
+// ---- spans of the weight streams ----------------------------------------------------------------------------------
+// What a kernel takes: where its weight stream starts and how many LDS stages it walks.  n_stages == 0: the span was refused -- empty
+// (the net's shape has no such stream) or not a whole number of stages (a layout mistake in plan.cpp).  The entry point then returns
+// I2SDF_EINVAL instead of launching a kernel whose DMA look-ahead would run past, or stop short of, the ops it consumes.
+namespace i2sdf {
+struct Span { const float* w = nullptr; int n_stages = 0; };
+inline int64_t span_chunks(const NetPlan& np, SpanId id) { return np.mark[id.to] - np.mark[id.from]; }
+inline Span span(const i2sdf_plan* p, const float* packed, const NetPlan& np, SpanId id) {
+  const int64_t n = span_chunks(np, id);
+  if (n <= 0 || n % id.stage_chunks) return Span{};
+  return Span{packed + p->scale_floats + np.mark[id.from] * CHUNK_FLOATS, (int)(n / id.stage_chunks)};
+}
+}  // namespace i2sdf
 
 // ---- point ranges ("parts") ---------------------------------------------------------------------------------------
 // A launch over M points of 128-point workgroups on 256 CUs runs ceil(M/128/256) rounds, the last one partly empty, and the
@@ -136,3 +168,52 @@ struct ChainGuard {
 // Launch order at the call sites: fork, tail (few long workgroups), full workgroups on `st`, join.
 hipStream_t i2sdf_tail_fork(const i2sdf_plan* p, hipStream_t st);
 void i2sdf_tail_join(const i2sdf_plan* p, hipStream_t st, hipStream_t side);
+
+// Split of a launch over M points into full rounds of 128-point workgroups (one per CU) and a short tail that is run by
+// the split-K kernels (ksplit.h): returns the number of points of the bulk part (0 = no split).
+inline int64_t split_bulk_points(int64_t M, int n_cu) {
+  const int64_t n_wg = (M + i2sdf::PTS_PER_WG - 1) / i2sdf::PTS_PER_WG;
+  const int64_t full = (n_wg / n_cu) * n_cu, rem = n_wg - full;
+  if (full == 0 || rem == 0 || rem * 4 > n_cu) return 0;      // nothing to gain, or the tail would not fit one round
+  // the bulk is also where the blocked layout of the saved tensors ends, and the weight-gradient kernels pick an operand's layout once
+  // per split-M chunk: a chunk must not straddle that boundary (n_cu * 128 is a multiple of the 2048-point chunk only when n_cu % 16 == 0
+  // -- true for the 256 CUs of an MI355X, not for every partition of it).  No split then: every point goes through the full
+  // workgroups, every saved tensor is blocked throughout.
+  if ((full * i2sdf::PTS_PER_WG) % I2SDF_WG_CH != 0) return 0;
+  return full * i2sdf::PTS_PER_WG;
+}
+
+// The three shapes of a per-point entry point's launches, with
+//   full(stream, first_workgroup, n_workgroups, M_visible) : 128-point workgroups; points >= M_visible are masked
+//   tail(stream, first_point)                              : the split-K kernel over the points from first_point on
+// ranged    : one `full` per non-empty point range on the range's stream (the caller says whether its kernel family is on the ranged path);
+// bulk+tail : when `may_split` (the entry point's own condition) and split_bulk_points() finds a partial last round.  TAIL_FORKED: tail first on
+//             the side stream of i2sdf_tail_fork, full workgroups on `st`, join (the SDF entry points).  TAIL_BEHIND: full workgroups, then the
+//             tail behind them on `st` (the radiance entry points: that tail is 32 short workgroups, the fork/join costs more than the
+//             overlap gains -- measured);
+// whole     : one `full` over the batch.
+enum TailOrder { TAIL_FORKED, TAIL_BEHIND };
+template <class Full, class Tail>
+inline void i2sdf_dispatch_points(const i2sdf_plan* p, hipStream_t st, int64_t M, bool ranged, bool may_split, TailOrder order, Full full, Tail tail) {
+  constexpr int64_t WG = i2sdf::PTS_PER_WG;
+  if (ranged) {
+    PartRun pr;
+    i2sdf_parts_begin(p, st, M, &pr);
+    for (int q = 0; q < pr.n; ++q)
+      if (pr.hi[q] > pr.lo[q]) full(pr.st[q], (int)(pr.lo[q] / WG), (unsigned)((pr.hi[q] - pr.lo[q] + WG - 1) / WG), M);
+    i2sdf_parts_end(p, st, &pr);
+    return;
+  }
+  const int64_t bulk = may_split ? split_bulk_points(M, p->n_cu) : 0;
+  if (bulk == 0) {
+    full(st, 0, (unsigned)((M + WG - 1) / WG), M);
+  } else if (order == TAIL_FORKED) {
+    hipStream_t ts = i2sdf_tail_fork(p, st);
+    tail(ts, bulk);
+    full(st, 0, (unsigned)(bulk / WG), bulk);
+    i2sdf_tail_join(p, st, ts);
+  } else {
+    full(st, 0, (unsigned)(bulk / WG), bulk);
+    tail(st, bulk);
+  }
+}

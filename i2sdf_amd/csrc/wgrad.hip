@@ -1149,7 +1149,6 @@ extern "C" int i2sdf_weight_grads(const i2sdf_plan* p, const i2sdf_train_buffers
     }
   }
   const bool has_light = p->light.d.n_lin > 0 && Mm > 0 && tb->gal0;
-  size_t light_first = tl.tasks.size();
   if (has_light) {  // ---- light head: l=0: A = G(a_0), B = relu(feature) ; l=1: A = G(a_1), B = softplus acts
     const NetPlan& np = p->light;
     const int H = np.d.hidden, F = p->F;
@@ -1158,7 +1157,6 @@ extern "C" int i2sdf_weight_grads(const i2sdf_plan* p, const i2sdf_train_buffers
     tl.add_block(np.wgrad_off[1], np.wg_cols[1], np.wgrad_off[1] + (int64_t)np.wg_rows[1] * np.wg_cols[1], {{tb->gal_last, 4, 4}}, {}, {0},
                  {Mm}, {{tb->hl, H, H}}, {}, 0, false);
   }
-  (void)light_first;
   // group the tiles by operand shape (narrow operands run 4x / 2x fewer MFMAs per point pair), longest first inside a group
   auto variant = [](const WgTask& x) {
     return x.j[0].a_w == 256 ? 4 : (x.j[0].a_w <= 32 ? 1 : (x.j[0].b_w <= 32 ? 2 : (x.j[0].b_w <= 64 ? 3 : 0)));

@@ -182,7 +182,7 @@ def test_fresh_plan_defaults(lib):
 
 def test_new_plan_options_and_blocked_prefix(lib):
     """Round-2 options toggle on 256-wide nets; i2sdf_blocked_points follows the split of a launch into full rounds of 128-point
-    workgroups (one per CU, 256 without a device) and the split-K tail (csrc/mlp_common.h: split_bulk_points)."""
+    workgroups (one per CU, 256 without a device) and the split-K tail (csrc/plan.h: split_bulk_points)."""
     from i2sdf_amd.config import synthetic_conf, plumbing_conf
     h = lib.load()
     rc, plan, _, _ = _plan(lib, synthetic_conf())
