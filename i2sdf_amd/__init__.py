@@ -23,7 +23,8 @@ def __getattr__(name):
     if name in ("GridAxes", "uniform_axes", "aligned_axes", "pca_frame"):
         from . import grid
         return getattr(grid, name)
-    if name in ("marching_cubes", "Mesh", "face_components", "largest_component", "sample_surface", "compact"):
+    if name in ("marching_cubes", "Mesh", "face_components", "largest_component", "sample_surface", "compact",
+                "voxel_down_sample", "nearest_neighbors", "evaluate"):
         from . import mesh
         return getattr(mesh, name)
     if name == "RenderEngine":

@@ -161,6 +161,26 @@ SIGNATURES = {
     "i2sdf_mesh_compact_gather": (C.c_int, [_P, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _P]),
     # verts, n_verts, faces, F, cdf, u_face, u_bary, count, points, face_index, status, stream
     "i2sdf_mesh_sample_surface": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _P, _I64, _P, _P, _P, _P]),
+    # points, n, bounds, status, stream
+    "i2sdf_points_bounds": (C.c_int, [_P, _I64, _P, _P, _P]),
+    # points, n, bounds, voxel_size, keys, status, stream
+    "i2sdf_points_voxel_keys": (C.c_int, [_P, _I64, _P, _D, _P, _P, _P]),
+    # sorted_keys, n, heads, stream
+    "i2sdf_points_voxel_heads": (C.c_int, [_P, _I64, _P, _P]),
+    # points, n, sorted_keys, perm, head_scan, out_points, out_counts, cap_m, stream
+    "i2sdf_points_voxel_mean": (C.c_int, [_P, _I64, _P, _P, _P, _P, _P, _I64, _P]),
+    "i2sdf_points_grid_workspace_bytes": (_I64, [_I64]),
+    # ref, n_ref, workspace, keys, status, stream
+    "i2sdf_points_grid_keys": (C.c_int, [_P, _I64, _P, _P, _P, _P]),
+    # ref, n_ref, sorted_keys, perm, workspace, sorted_ref, stream
+    "i2sdf_points_grid_build": (C.c_int, [_P, _I64, _P, _P, _P, _P, _P]),
+    # query, n_query, sorted_ref, n_ref, workspace, max_ring, dist, index, fallback_list, status, stream
+    "i2sdf_points_nn_query": (C.c_int, [_P, _I64, _P, _I64, _P, _I32, _P, _P, _P, _P, _P]),
+    # query, n_query, ref, n_ref, fallback_list, status, dist, index, stream
+    "i2sdf_points_nn_fallback": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _P, _P, _P]),
+    "i2sdf_points_reduce_workspace_bytes": (_I64, [_I64]),
+    # dist, n, threshold, workspace, out, stream
+    "i2sdf_points_threshold_reduce": (C.c_int, [_P, _I64, _D, _P, _P, _P]),
     # pred, target, channels, pixel_idx, first_pixel, n, pointlinks, n_links, pdf_max, pdf_prune, pdf, n_pdf, n_bad, stream
     "i2sdf_pdf_update": (C.c_int, [_P, _P, _I32, _P, _I64, _I64, _P, _I64, C.c_double, C.c_double, _P, _I64, _P, _P]),
     # seed, B, n_eval, n_samples, n_extra, max_iters, n_z, eik_radius, nbr_half_width, strat_u, cdf_u, extra_idx, eik_idx, eik_pts, nbr_off, stream

@@ -17,6 +17,16 @@ Mesh operations on the device (csrc/meshops.hip), the trimesh calls between the 
   * sample_surface     `trimesh.sample.sample_surface(mesh, count)` (utils/plots.py:286, model/eval/recon.py:62) with explicit
                        uniform draws, so that a run can be repeated and checked.
 All of them are bitwise reproducible from run to run (integer atomics only, fp64 sums in a fixed order).
+
+Scoring on the device (csrc/pointops.hip), the step the reference takes right after the export (utils/mesh_util.py:evaluate,
+called by model/eval/recon.py:111-129, where open3d and a scikit-learn KDTree run on the host):
+  * voxel_down_sample  open3d's `voxel_down_sample` rule (mesh_util.py:32-34) with pinned arithmetic: voxel indices in fp64, every
+                       mean an fp64 sum in original index order; voxels in ascending (ix, iy, iz) order, not a hash map's;
+  * nearest_neighbors  `KDTree(ref).query(query)` (mesh_util.py:12-22): exact fp32 distances and indices through a uniform grid
+                       with a shell search and a brute-force second pass for the queries the grid cannot answer cheaply;
+  * evaluate           Acc / Comp / Prec / Recal / F-score (mesh_util.py:25-52) of two vertex sets.  It scores whatever vertex
+                       sets it is given; the reference's visibility culling (mesh_util.refuse) is not part of this library.
+These are bitwise reproducible as well.
 """
 from __future__ import annotations
 
@@ -247,3 +257,183 @@ def sample_surface(mesh, count: int, draws=None, generator=None, _check=True):
         if _check:                                 # (extract_mesh_high_res samples meshes the library made itself)
             L.check(lib.i2sdf_mesh_status(L.ptr(status), st), "sample_surface: face indices")
     return points, face_index
+
+
+# ------------------------------------------------------------------------------------------------ scoring (csrc/pointops.hip)
+def _points_arg(x, what, name):
+    """(n, 3) fp32 device points of a Mesh / (verts, faces, ...) tuple or of a bare tensor."""
+    if not torch.is_tensor(x):
+        if not isinstance(x, (tuple, list)) or len(x) == 0:
+            raise ValueError(f"{what}: {name} must be a (n, 3) fp32 tensor on a GPU or a Mesh")
+        x = x[0]
+    if not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != 3:
+        raise ValueError(f"{what}: {name} must be a (n, 3) fp32 tensor on a GPU")
+    if x.shape[0] > 2 ** 31 - 1:
+        raise ValueError(f"{what}: {name} must hold at most 2^31 - 1 points")
+    return x.contiguous()
+
+
+def _points_status(dev):
+    return torch.zeros(2, dtype=torch.int32, device=dev)       # (flags, fallback count): include/i2sdf.h
+
+
+def _raise_points_status(flags, what):
+    if flags & 1:
+        raise L.I2SDFError(f"{what} failed (-1): a coordinate is not finite")
+    if flags & 2:
+        raise L.I2SDFError(f"{what} failed (-1): a voxel index does not fit 21 bits per axis (voxel_size too small for the extent)")
+
+
+@torch.no_grad()
+def voxel_down_sample(points: torch.Tensor, voxel_size: float, _stats=None):
+    """open3d's `PointCloud.voxel_down_sample(voxel_size)` (utils/mesh_util.py:evaluate) on the device ->
+    (points_out (M, 3) fp32, counts (M,) int32): the mean of the points of every occupied voxel, where
+    lo = min(points) - voxel_size / 2 per axis and a point's voxel is floor((p - lo) / voxel_size), computed in fp64 from the fp32
+    coordinates.  Each mean is the fp64 sum of the voxel's points in original index order, divided by their number, rounded to
+    fp32.  Voxels come in ascending (ix, iy, iz) order (open3d's order is that of its hash map).  Bitwise reproducible from run
+    to run.  A non-finite coordinate, or a voxel index beyond 21 bits per axis, raises I2SDFError.  One host synchronisation
+    reads M (and the validation word)."""
+    pts = _points_arg(points, "voxel_down_sample", "points")
+    voxel_size = float(voxel_size)
+    if not (voxel_size > 0.0) or voxel_size == float("inf"):
+        raise ValueError("voxel_down_sample: voxel_size must be positive and finite")
+    N, dev = pts.shape[0], pts.device
+    if N == 0:
+        return torch.empty(0, 3, dtype=torch.float32, device=dev), torch.empty(0, dtype=torch.int32, device=dev)
+    lib = L.load()
+    ev = _marker(_stats)
+    with torch.cuda.device(dev):
+        st = L.stream_ptr()
+        status = _points_status(dev)
+        bounds = torch.empty(8, dtype=torch.int32, device=dev)
+        keys = torch.empty(N, dtype=torch.int64, device=dev)
+        heads = torch.empty(N, dtype=torch.int32, device=dev)
+        ev("start")
+        L.check(lib.i2sdf_points_bounds(L.ptr(pts), N, L.ptr(bounds), L.ptr(status), st), "i2sdf_points_bounds")
+        L.check(lib.i2sdf_points_voxel_keys(L.ptr(pts), N, L.ptr(bounds), voxel_size, L.ptr(keys), L.ptr(status), st),
+                "i2sdf_points_voxel_keys")
+        skeys, perm = torch.sort(keys, stable=True)            # stable: a voxel's points stay in original index order
+        del keys
+        ev("voxel_keys_sort")
+        L.check(lib.i2sdf_points_voxel_heads(L.ptr(skeys), N, L.ptr(heads), st), "i2sdf_points_voxel_heads")
+        scan = torch.cumsum(heads, 0, dtype=torch.int32)
+        M, flags = torch.cat([scan[-1:], status[:1]]).tolist()
+        _raise_points_status(flags, "voxel_down_sample")
+        out = torch.empty(M, 3, dtype=torch.float32, device=dev)
+        counts = torch.empty(M, dtype=torch.int32, device=dev)
+        L.check(lib.i2sdf_points_voxel_mean(L.ptr(pts), N, L.ptr(skeys), L.ptr(perm), L.ptr(scan), L.ptr(out), L.ptr(counts), M, st),
+                "i2sdf_points_voxel_mean")
+        ev("voxel_mean")
+    return out, counts
+
+
+def _marker(stats):
+    """ev(label): appends (label, event recorded now) to `stats`, the per-stage record scripts/mesh_eval_timing.py reads."""
+    if stats is None:
+        return lambda label: None
+
+    def ev(label):
+        e = torch.cuda.Event(enable_timing=True)
+        e.record()
+        stats.append((label, e))
+    return ev
+
+
+def _ring_budget(R):
+    """Shells a query may search before it goes to the brute-force pass: as long as a shell block's cells ((2r + 1)^3) stay
+    below the R / 32 a wave-per-query pass over R points costs per lane, and never more than 8."""
+    r = 1
+    while r < 8 and (2 * (r + 1) + 1) ** 3 <= R // 32:
+        r += 1
+    return r
+
+
+@torch.no_grad()
+def nearest_neighbors(query: torch.Tensor, ref: torch.Tensor, _stats=None):
+    """Exact Euclidean nearest neighbour of every query among `ref` -> (dist (Q,) fp32, index (Q,) int32), what
+    `sklearn.neighbors.KDTree(ref).query(query)` returns (utils/mesh_util.py:nn_correspondance).  Distances are computed in fp32
+    from fp32 differences; equal distances go to the smallest reference index.  Exact wherever the query lies: `ref` is hashed
+    into a uniform grid (whose cell count is capped whatever the bounding box), every query searches shells of cells around its
+    own until the best distance is inside the searched shell, and the queries that exhaust a small shell budget (far from the
+    cloud, or in its large empty parts) are answered by a brute-force pass over `ref`, one wave per query.
+    Q = 0 gives empty tensors; R = 0 raises ValueError, a non-finite coordinate I2SDFError.  One host synchronisation reads the
+    validation word."""
+    q = _points_arg(query, "nearest_neighbors", "query")
+    r = _points_arg(ref, "nearest_neighbors", "ref")
+    if q.device != r.device:
+        raise ValueError("nearest_neighbors: query and ref must be on the same device")
+    Q, R, dev = q.shape[0], r.shape[0], q.device
+    if R == 0:
+        raise ValueError("nearest_neighbors: ref is empty")
+    dist = torch.empty(Q, dtype=torch.float32, device=dev)
+    index = torch.empty(Q, dtype=torch.int32, device=dev)
+    lib = L.load()
+    ev = _marker(_stats)
+    with torch.cuda.device(dev):
+        st = L.stream_ptr()
+        status = _points_status(dev)
+        ws = torch.empty(int(lib.i2sdf_points_grid_workspace_bytes(R)), dtype=torch.uint8, device=dev)
+        keys = torch.empty(R, dtype=torch.int64, device=dev)
+        sref = torch.empty(R, 4, dtype=torch.float32, device=dev)
+        fb = torch.empty(max(Q, 1), dtype=torch.int32, device=dev)
+        ev("start")
+        L.check(lib.i2sdf_points_grid_keys(L.ptr(r), R, L.ptr(ws), L.ptr(keys), L.ptr(status), st), "i2sdf_points_grid_keys")
+        skeys, perm = torch.sort(keys, stable=True)            # stable: a cell's points stay in ascending index order
+        del keys
+        L.check(lib.i2sdf_points_grid_build(L.ptr(r), R, L.ptr(skeys), L.ptr(perm), L.ptr(ws), L.ptr(sref), st), "i2sdf_points_grid_build")
+        ev("grid_build")
+        if Q > 0:
+            L.check(lib.i2sdf_points_nn_query(L.ptr(q), Q, L.ptr(sref), R, L.ptr(ws), _ring_budget(R), L.ptr(dist), L.ptr(index), L.ptr(fb),
+                                              L.ptr(status), st), "i2sdf_points_nn_query")
+            ev("nn_query")
+            L.check(lib.i2sdf_points_nn_fallback(L.ptr(q), Q, L.ptr(r), R, L.ptr(fb), L.ptr(status), L.ptr(dist), L.ptr(index), st),
+                    "i2sdf_points_nn_fallback")
+            ev("nn_fallback")
+        flags, n_fb = status.tolist()
+        if _stats is not None:
+            _stats.append(("fallback_count", n_fb))
+        _raise_points_status(flags, "nearest_neighbors")
+    return dist, index
+
+
+@torch.no_grad()
+def evaluate(pred, trgt, threshold: float = 0.05, down_sample: float = 0.02, _stats=None) -> dict:
+    """`utils/mesh_util.py:evaluate` (model/eval/recon.py:111-129) on the device: both vertex sets are voxel down-sampled
+    (a falsy `down_sample` skips that), nearest neighbours are found in both directions, and
+        'Acc' = mean(dist2), 'Comp' = mean(dist1), 'Prec' = mean(dist2 < threshold), 'Recal' = mean(dist1 < threshold),
+        'F-score' = 2 Prec Recal / (Prec + Recal)   (NaN when both are 0, as numpy gives it)
+    come back as Python floats, where dist1 is the distance of each trgt point to its nearest pred point and dist2 that of each
+    pred point to its nearest trgt point.  The means are fp64 sums in a fixed order, the counts integers; one download of the
+    five numbers ends the call.
+    `pred`, `trgt`: a Mesh / (verts, faces, ...) tuple or a bare (n, 3) fp32 device tensor; only vertices are used, as in the
+    reference.  The function scores whatever vertex sets it is given: the reference first culls what no camera sees
+    (mesh_util.refuse, a pyrender depth render re-fused into an open3d TSDF), which is not part of this library, so without that
+    culling the numbers are not comparable with the paper's.  An empty set (after down-sampling) raises ValueError."""
+    p = _points_arg(pred, "evaluate", "pred")
+    t = _points_arg(trgt, "evaluate", "trgt")
+    if p.device != t.device:
+        raise ValueError("evaluate: pred and trgt must be on the same device")
+    threshold = float(threshold)
+    if threshold != threshold:
+        raise ValueError("evaluate: threshold is NaN")
+    if down_sample:
+        p, _ = voxel_down_sample(p, down_sample, _stats=_stats)
+        t, _ = voxel_down_sample(t, down_sample, _stats=_stats)
+    if p.shape[0] == 0 or t.shape[0] == 0:
+        raise ValueError(f"evaluate: an empty point set ({p.shape[0]} pred, {t.shape[0]} trgt points)")
+    dist1, _ = nearest_neighbors(t, p, _stats=_stats)
+    dist2, _ = nearest_neighbors(p, t, _stats=_stats)
+    lib = L.load()
+    dev = p.device
+    with torch.cuda.device(dev):
+        st = L.stream_ptr()
+        sums = torch.empty(2, 2, dtype=torch.float64, device=dev)                  # rows: dist2 (pred), dist1 (trgt); (sum, count)
+        for row, d in enumerate((dist2, dist1)):
+            ws = torch.empty(int(lib.i2sdf_points_reduce_workspace_bytes(d.shape[0])), dtype=torch.uint8, device=dev)
+            L.check(lib.i2sdf_points_threshold_reduce(L.ptr(d), d.shape[0], threshold, L.ptr(ws), L.ptr(sums[row]), st),
+                    "i2sdf_points_threshold_reduce")
+        # [[Acc, Prec], [Comp, Recal]]; the divisor is a tensor: a Python scalar would be turned into a multiplication by 1 / n
+        m = sums / torch.tensor([[float(dist2.shape[0])], [float(dist1.shape[0])]], dtype=torch.float64, device=dev)
+        f = 2.0 * m[0, 1] * m[1, 1] / (m[0, 1] + m[1, 1])
+        acc, prec, comp, recal, fscore = torch.cat([m.reshape(-1), f.reshape(1)]).tolist()
+    return {"Acc": acc, "Comp": comp, "Prec": prec, "Recal": recal, "F-score": fscore}

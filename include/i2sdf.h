@@ -665,6 +665,57 @@ int i2sdf_mesh_sample_surface(const float* verts, int64_t n_verts, const int32_t
                               int32_t* status, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Point-set operations (csrc/pointops.hip) -- the scoring step after the mesh export (utils/mesh_util.py:evaluate, called by
+ * model/eval/recon.py:111-129, where open3d and a scikit-learn KDTree run on the host): voxel down-sampling, exact nearest
+ * neighbours, thresholded means.  points / query / ref (n, 3) fp32, device; counts <= INT32_MAX (else I2SDF_EINVAL).  Every call
+ * only enqueues on `stream`: no allocation, no synchronisation; arguments are validated on the host before any launch.  Results
+ * are bitwise reproducible: integer atomics only, fp64 sums in a fixed order.
+ *   status   device int32[2], zeroed by the caller.  status[0]: bit 0 <- a non-finite coordinate, bit 1 <- a voxel index that
+ *            does not fit 21 bits; status[1]: the number of queries handed to the fallback pass.  The caller reads it back.
+ *   bounds   device int32[8], opaque: the per-axis minima / maxima of the finite coordinates.
+ *   _bounds            bounds <- those of points (n may be 0)
+ *   _voxel_keys        open3d's VoxelDownSample rule in fp64: lo = min - voxel_size / 2, index = floor((p - lo) / voxel_size) per
+ *                      axis, keys[i] = ix << 42 | iy << 21 | iz (INT64_MAX and a status bit for a point that has no key).
+ *                      voxel_size must be positive and finite                                                          (n) int64
+ *   _voxel_heads       sorted_keys (n) ascending, a STABLE sort by the caller: heads[i] = 1 where a run of equal keys begins  (n) int32
+ *   _voxel_mean        perm (n) int64 = the position each sorted entry came from, head_scan = INCLUSIVE int32 running sum of
+ *                      heads (by the caller, whose last entry M sizes the outputs).  Voxel m (in ascending key order, that is
+ *                      (ix, iy, iz) lexicographic): out_points[m] = fp32(fp64 sum of its points in original index order / count),
+ *                      out_counts[m] = count.  Voxels beyond cap_m are not written                       (M, 3) fp32, (M) int32
+ *   _grid_keys         hashes ref into a uniform grid over its bounding box, described at the head of `workspace`
+ *                      (i2sdf_points_grid_workspace_bytes(n_ref) bytes, 0 for n_ref outside [1, INT32_MAX]): about 2 cells per
+ *                      point, at most 1024 per axis and 2^22 in all -- the cell is enlarged until the grid fits the tables, whatever
+ *                      the bounding box.  keys[i] = linear cell of ref[i]                                          (n_ref) int64
+ *   _grid_build        sorted_keys / perm: the caller's STABLE sort of those keys.  Fills the cell start / end tables in
+ *                      `workspace` and sorted_ref[i] = (x, y, z, bits of the original index) of sorted entry i  (n_ref, 4) fp32
+ *   _nn_query          one query per lane: shells of cells of growing Chebyshev radius r <= max_ring around the query's cell
+ *                      (clamped into the grid); ends once the best distance is within r cells or the shells cover the grid.
+ *                      dist[q] = fp32 Euclidean distance (fp32 differences, squares and sums rounded separately), index[q] = the
+ *                      reference index, the smallest among equal distances.  A query that exhausts max_ring gets a provisional
+ *                      answer and is appended to fallback_list (n_query) int32, counted in status[1].  A non-finite query sets
+ *                      status[0] and gets (NaN, -1)                                             (n_query) fp32, (n_query) int32
+ *   _nn_fallback       answers the status[1] listed queries exactly: one wave per query over all of ref (original order)
+ *   _threshold_reduce  out[0] = fp64 sum of dist, out[1] = count(dist < threshold) as fp64, in a fixed order; workspace of
+ *                      i2sdf_points_reduce_workspace_bytes(n) bytes; n >= 1                                     device fp64[2]
+ * ---------------------------------------------------------------------------------------------- */
+int i2sdf_points_bounds(const float* points, int64_t n, int32_t* bounds, int32_t* status, void* stream);
+int i2sdf_points_voxel_keys(const float* points, int64_t n, const int32_t* bounds, double voxel_size, int64_t* keys, int32_t* status,
+                            void* stream);
+int i2sdf_points_voxel_heads(const int64_t* sorted_keys, int64_t n, int32_t* heads, void* stream);
+int i2sdf_points_voxel_mean(const float* points, int64_t n, const int64_t* sorted_keys, const int64_t* perm, const int32_t* head_scan,
+                            float* out_points, int32_t* out_counts, int64_t cap_m, void* stream);
+int64_t i2sdf_points_grid_workspace_bytes(int64_t n_ref);
+int i2sdf_points_grid_keys(const float* ref, int64_t n_ref, void* workspace, int64_t* keys, int32_t* status, void* stream);
+int i2sdf_points_grid_build(const float* ref, int64_t n_ref, const int64_t* sorted_keys, const int64_t* perm, void* workspace,
+                            float* sorted_ref, void* stream);
+int i2sdf_points_nn_query(const float* query, int64_t n_query, const float* sorted_ref, int64_t n_ref, const void* workspace,
+                          int32_t max_ring, float* dist, int32_t* index, int32_t* fallback_list, int32_t* status, void* stream);
+int i2sdf_points_nn_fallback(const float* query, int64_t n_query, const float* ref, int64_t n_ref, const int32_t* fallback_list,
+                             const int32_t* status, float* dist, int32_t* index, void* stream);
+int64_t i2sdf_points_reduce_workspace_bytes(int64_t n);
+int i2sdf_points_threshold_reduce(const float* dist, int64_t n, double threshold, void* workspace, double* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Bubble-PDF update (row N4) -- VolumeRenderSystem.update_pdf fused with the error it is fed (model/trainer/recon.py:142-152,
  * :195-199 in the initial sweep over all images, :246-252 every training step):
  *   channels == 1: v = |pred - target|                         (criterion DEPTH: depth_values vs depth image)
