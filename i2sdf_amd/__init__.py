@@ -24,7 +24,8 @@ def __getattr__(name):
         from . import grid
         return getattr(grid, name)
     if name in ("marching_cubes", "Mesh", "face_components", "largest_component", "sample_surface", "compact",
-                "voxel_down_sample", "nearest_neighbors", "evaluate"):
+                "voxel_down_sample", "nearest_neighbors", "evaluate", "mesh_depth", "tsdf_fuse", "tsdf_integrate", "tsdf_extract",
+                "TsdfVolume", "refuse", "score"):
         from . import mesh
         return getattr(mesh, name)
     if name == "RenderEngine":

@@ -76,6 +76,8 @@ OPT_SAMPLER_BF16X2 = 1024
 OPT_SAVES24 = 2048
 MAX_PARTS = 4
 GRID_ORDER_MESHGRID, GRID_ORDER_VOLUME = 0, 1
+RASTER_SMALL_MAX = 64            # I2SDF_RASTER_SMALL_MAX
+TSDF_MAX_CELLS = 1 << 24         # I2SDF_TSDF_MAX_CELLS
 
 
 class I2SDFError(RuntimeError):
@@ -181,6 +183,23 @@ SIGNATURES = {
     "i2sdf_points_reduce_workspace_bytes": (_I64, [_I64]),
     # dist, n, threshold, workspace, out, stream
     "i2sdf_points_threshold_reduce": (C.c_int, [_P, _I64, _D, _P, _P, _P]),
+    "i2sdf_raster_workspace_bytes": (_I64, [_I64, _I64, _I32]),
+    # verts, n_verts, faces, F, w2c, n_cam, K4 (host), H, W, znear, zfar, cull, workspace, depth, counters, status, stream
+    "i2sdf_raster_depth": (C.c_int, [_P, _I64, _P, _I64, _P, _I32, _P, _I32, _I32, _F, _F, _I32, _P, _P, _P, _P, _P]),
+    "i2sdf_tsdf_table_cells": (_I64, [_P]),
+    "i2sdf_tsdf_extract_workspace_bytes": (_I64, [_I64]),
+    # depths, n_cam, H, W, c2w, K4 (host), voxel_length, unit_length, sdf_trunc, depth_trunc, stride, bounds, stream
+    "i2sdf_tsdf_bounds": (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _F, _F, _F, _F, _I32, _P, _P]),
+    # depths, n_cam, cam, H, W, c2w, K4, voxel_length, unit_length, sdf_trunc, depth_trunc, stride, grid6 (host), slot, n_units, stamp,
+    # list, list_count, flag, stream
+    "i2sdf_tsdf_mark": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _F, _F, _F, _F, _I32, _P, _P, _I64, _P, _P, _P, _P, _P]),
+    # depths, n_cam, cam, H, W, w2c, K4, voxel_length, unit_length, sdf_trunc, depth_trunc, grid6, unit_cell, n_units, list, list_count,
+    # tsdf, weight, stream
+    "i2sdf_tsdf_integrate": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _F, _F, _F, _F, _P, _P, _I64, _P, _P, _P, _P, _P]),
+    # grid6, slot, unit_cell, n_units, tsdf, weight, workspace, blocks, stream
+    "i2sdf_tsdf_count": (C.c_int, [_P, _P, _P, _I64, _P, _P, _P, _P, _P]),
+    # grid6, voxel_length, unit_length, slot, unit_cell, n_units, tsdf, weight, workspace, blocks_excl, verts, normals, faces, cap_v, cap_f, stream
+    "i2sdf_tsdf_emit": (C.c_int, [_P, _F, _F, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _P]),
     # pred, target, channels, pixel_idx, first_pixel, n, pointlinks, n_links, pdf_max, pdf_prune, pdf, n_pdf, n_bad, stream
     "i2sdf_pdf_update": (C.c_int, [_P, _P, _I32, _P, _I64, _I64, _P, _I64, C.c_double, C.c_double, _P, _I64, _P, _P]),
     # seed, B, n_eval, n_samples, n_extra, max_iters, n_z, eik_radius, nbr_half_width, strat_u, cdf_u, extra_idx, eik_idx, eik_pts, nbr_off, stream

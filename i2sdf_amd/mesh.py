@@ -25,8 +25,20 @@ called by model/eval/recon.py:111-129, where open3d and a scikit-learn KDTree ru
   * nearest_neighbors  `KDTree(ref).query(query)` (mesh_util.py:12-22): exact fp32 distances and indices through a uniform grid
                        with a shell search and a brute-force second pass for the queries the grid cannot answer cheaply;
   * evaluate           Acc / Comp / Prec / Recal / F-score (mesh_util.py:25-52) of two vertex sets.  It scores whatever vertex
-                       sets it is given; the reference's visibility culling (mesh_util.refuse) is not part of this library.
+                       sets it is given; `score` first culls what no camera sees, as the reference does.
 These are bitwise reproducible as well.
+
+Visibility culling on the device (csrc/raster.hip, csrc/tsdf.hip), the step between the export and the scores
+(model/eval/recon.py:111-125 -> utils/mesh_util.py:refuse, pyrender on EGL and open3d on the host in the reference):
+  * mesh_depth         the depth render of every camera: fp64 edge functions, top-left rule, a 32-bit atomicMin per sample;
+  * tsdf_integrate     open3d's ScalableTSDFVolume.integrate into 16^3-voxel units allocated where cameras touch them;
+  * tsdf_extract       its extract_triangle_mesh by this module's marching cubes, across unit borders;
+  * tsdf_fuse          the two together (the reference's depth2mesh); refuse = mesh_depth + tsdf_fuse; score = refuse, refuse, evaluate.
+Bitwise reproducible too.  Neither open3d nor pyrender is available where this library is developed: the fusion rule and the depth
+convention are restated from their sources and checked against a numpy restatement and closed-form geometry, not against them.  Not
+imitated: OpenGL's 24-bit depth buffer (pyrender reads depth back through it: a relative error of about 6e-8 z / znear), open3d's
+incremental fp32 accumulation of voxel coordinates, its table for ambiguous cells, its hash map's vertex order.  The scores are the
+reference's up to those effects.
 """
 from __future__ import annotations
 
@@ -407,8 +419,8 @@ def evaluate(pred, trgt, threshold: float = 0.05, down_sample: float = 0.02, _st
     five numbers ends the call.
     `pred`, `trgt`: a Mesh / (verts, faces, ...) tuple or a bare (n, 3) fp32 device tensor; only vertices are used, as in the
     reference.  The function scores whatever vertex sets it is given: the reference first culls what no camera sees
-    (mesh_util.refuse, a pyrender depth render re-fused into an open3d TSDF), which is not part of this library, so without that
-    culling the numbers are not comparable with the paper's.  An empty set (after down-sampling) raises ValueError."""
+    (mesh_util.refuse, a pyrender depth render re-fused into an open3d TSDF); `score` does that first (refuse, refuse, evaluate) and
+    says how far its culling is the reference's.  An empty set (after down-sampling) raises ValueError."""
     p = _points_arg(pred, "evaluate", "pred")
     t = _points_arg(trgt, "evaluate", "trgt")
     if p.device != t.device:
@@ -437,3 +449,320 @@ def evaluate(pred, trgt, threshold: float = 0.05, down_sample: float = 0.02, _st
         f = 2.0 * m[0, 1] * m[1, 1] / (m[0, 1] + m[1, 1])
         acc, prec, comp, recal, fscore = torch.cat([m.reshape(-1), f.reshape(1)]).tolist()
     return {"Acc": acc, "Comp": comp, "Prec": prec, "Recal": recal, "F-score": fscore}
+
+
+# ------------------------------------------------------------------- visibility culling (csrc/raster.hip, csrc/tsdf.hip)
+class TsdfVolume(NamedTuple):
+    """A block-sparse TSDF volume: 16^3-voxel units, allocated where a camera touched them, in ascending (ix, iy, iz) order."""
+    tsdf: torch.Tensor       # (n_units, 4096) fp32; voxel (i, j, k) of a unit at i << 8 | j << 4 | k
+    weight: torch.Tensor     # (n_units, 4096) fp32: the number of cameras that updated the voxel
+    units: torch.Tensor      # (n_units, 3) int32 unit indices: a unit spans [index, index + 1) * 16 * voxel_length
+    slot: torch.Tensor       # (dims) int32: the unit's row in tsdf / weight, -1 where there is none; cell [0, 0, 0] is unit `origin`
+    origin: tuple            # lowest unit index per axis
+    voxel_length: float
+    sdf_trunc: float
+
+
+def _f32(x):
+    import ctypes as C
+    return C.c_float(float(x)).value
+
+
+def _intrinsics(K, what):
+    """(fx, fy, cx, cy) of a 3x3 or 4x4 intrinsic matrix, read as utils/mesh_util.py:refuse reads them."""
+    try:
+        k = torch.as_tensor(K).detach().to("cpu", torch.float64)
+    except Exception:
+        raise ValueError(f"{what}: K must be a 3x3 or 4x4 matrix")
+    if k.dim() != 2 or tuple(k.shape) not in ((3, 3), (4, 4)):
+        raise ValueError(f"{what}: K must be a 3x3 or 4x4 matrix, got shape {tuple(k.shape)}")
+    fx, fy, cx, cy = (_f32(k[0, 0]), _f32(k[1, 1]), _f32(k[0, 2]), _f32(k[1, 2]))
+    if not (0.0 < fx < float("inf") and 0.0 < fy < float("inf") and abs(cx) < float("inf") and abs(cy) < float("inf")):
+        raise ValueError(f"{what}: K needs finite fx, fy > 0 and finite cx, cy (got {fx}, {fy}, {cx}, {cy})")
+    return fx, fy, cx, cy
+
+
+def camera_matrices(poses):
+    """(c2w, w2c): the (n_cam, 3, 4) fp32 CPU matrices the kernels read, from (n_cam, 4, 4) camera-to-world poses (any device, any
+    floating dtype; x right, y down, z forward, last row 0 0 0 1).  The inverse is the fp64 adjugate formula, rounded to fp32 once.
+    A pose that is not finite, not affine or not invertible raises ValueError."""
+    if not torch.is_tensor(poses):
+        try:
+            poses = torch.as_tensor(poses)
+        except Exception:
+            raise ValueError("poses must be a (n_cam, 4, 4) tensor")
+    if poses.dim() != 3 or tuple(poses.shape[1:]) != (4, 4) or not poses.dtype.is_floating_point:
+        raise ValueError(f"poses must be a (n_cam, 4, 4) floating-point tensor, got {tuple(poses.shape)} {poses.dtype}")
+    p = poses.detach().to("cpu", torch.float64)
+    if p.shape[0] > 65535:
+        raise ValueError("poses: at most 65535 cameras")
+    if not bool(torch.isfinite(p).all()):
+        raise ValueError("poses: a pose is not finite")
+    if p.shape[0] and not bool((p[:, 3] == torch.tensor([0.0, 0.0, 0.0, 1.0], dtype=torch.float64)).all()):
+        raise ValueError("poses: the last row of every pose must be (0, 0, 0, 1)")
+    A, t = p[:, :3, :3], p[:, :3, 3]
+    a, b, c = A[:, 0], A[:, 1], A[:, 2]                       # rows
+    adj = torch.stack([torch.cross(b, c, dim=1), torch.cross(c, a, dim=1), torch.cross(a, b, dim=1)], dim=2)   # columns of the adjugate
+    det = (a * torch.cross(b, c, dim=1)).sum(1)
+    scale = A.abs().amax(dim=(1, 2)) ** 3 if p.shape[0] else det
+    if p.shape[0] and not bool((det.abs() > 1e-12 * scale).all()):
+        raise ValueError("poses: a pose is not invertible")
+    inv = adj / det[:, None, None]
+    tinv = -(inv @ t[:, :, None])
+    w2c = torch.cat([inv, tinv], dim=2).to(torch.float32).contiguous()
+    c2w = p[:, :3, :].to(torch.float32).contiguous()
+    return c2w, w2c
+
+
+def _image_size(H, W, what):
+    H, W = int(H), int(W)
+    if H < 1 or W < 1 or H * W > 2 ** 31 - 1:
+        raise ValueError(f"{what}: H and W must be positive with H * W < 2^31 (got {H}, {W})")
+    return H, W
+
+
+def _k4(fx, fy, cx, cy):
+    import ctypes as C
+    return (C.c_float * 4)(fx, fy, cx, cy)
+
+
+@torch.no_grad()
+def mesh_depth(mesh, poses, K, H: int, W: int, znear: float = 0.05, zfar: float = 100.0, cull: str = "back", _stats=None) -> torch.Tensor:
+    """Depth maps (n_cam, H, W) fp32 of a device mesh from pinhole cameras -- the pyrender depth render of utils/mesh_util.py:refuse.
+    `poses` (n_cam, 4, 4) camera-to-world in the reference's convention (rend_util.load_K_Rt_from_P: x right, y down, z forward);
+    `K` 3x3 or 4x4, read as refuse reads it (fx = K[0, 0], fy = K[1, 1], cx = K[0, 2], cy = K[1, 2]).
+    depth[c, v, u] is the camera-space z of the nearest triangle crossed by the ray through ((u - cx) / fx, (v - cy) / fy, 1) -- the
+    pixel pyrender's IntrinsicsCamera draws at column u, row v and the pixel open3d's integration reads back -- and 0 where there is
+    none.  Samples (not triangles) with z outside [znear, zfar] give nothing (pyrender's default clip planes), so a triangle that
+    crosses the camera plane still covers the pixels of its part in front.  cull="back" drops triangles whose winding is clockwise as
+    the camera sees them (pyrender's default; the reference left SKIP_CULL_FACES commented out), cull="none" keeps both sides.  The
+    marching-cubes meshes of this library have right-hand normals towards increasing SDF, so they face cameras in free space.
+    Coverage is exact (fp64 edge functions, top-left rule) and the image is bitwise reproducible.  All depth maps stay resident on the
+    device (n_cam H W 4 bytes); the projected vertices are held for a chunk of cameras at a time.
+    Not imitated: OpenGL's 24-bit depth buffer, through which pyrender reads depth back (a relative error of about 6e-8 z / znear).
+    The convention is restated from pyrender's sources, not checked against a build of it.  An empty mesh or camera list gives zeros /
+    an empty tensor.  One host synchronisation reads the validation word."""
+    verts, faces, _ = _mesh_args(mesh[:2], "mesh_depth")
+    if cull not in ("back", "none"):
+        raise ValueError(f"mesh_depth: cull must be 'back' or 'none', got {cull!r}")
+    H, W = _image_size(H, W, "mesh_depth")
+    k4 = _intrinsics(K, "mesh_depth")
+    znear, zfar = float(znear), float(zfar)
+    if not (0.0 < znear <= zfar < float("inf")):
+        raise ValueError(f"mesh_depth: need 0 < znear <= zfar < inf (got {znear}, {zfar})")
+    c2w, w2c = camera_matrices(poses)
+    n_cam, V, F, dev = w2c.shape[0], verts.shape[0], faces.shape[0], verts.device
+    if n_cam * H * W > (2 ** 31 - 1) * 256:
+        raise ValueError("mesh_depth: too many pixels")
+    depth = torch.empty(n_cam, H, W, dtype=torch.float32, device=dev)
+    if n_cam == 0:
+        return depth
+    lib = L.load()
+    ev = _marker(_stats)
+    with torch.cuda.device(dev):
+        st = L.stream_ptr()
+        ws = None
+        if V and F:
+            nbytes = int(lib.i2sdf_raster_workspace_bytes(V, F, n_cam))
+            if nbytes <= 0:
+                raise ValueError("mesh_depth: mesh size not supported")
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        counters = torch.empty(n_cam, 2, dtype=torch.int32, device=dev)
+        status = _new_status(dev)
+        w2c_d = w2c.to(dev)
+        ev("start")
+        L.check(lib.i2sdf_raster_depth(L.ptr(verts), V, L.ptr(faces), F, L.ptr(w2c_d), n_cam, _k4(*k4), H, W, znear, zfar,
+                                       1 if cull == "back" else 0, L.ptr(ws), L.ptr(depth), L.ptr(counters), L.ptr(status), st),
+                "i2sdf_raster_depth")
+        ev("depth")
+        if int(status.item()):
+            raise _bad_faces("mesh_depth")
+        if _stats is not None:
+            _stats.append(("raster_counters", counters))
+    return depth
+
+
+def _tsdf_args(depths, poses, K, voxel_length, sdf_trunc, depth_trunc, stride, what):
+    if not torch.is_tensor(depths) or not depths.is_cuda or depths.dtype != torch.float32 or depths.dim() != 3:
+        raise ValueError(f"{what}: depths must be a (n_cam, H, W) fp32 tensor on a GPU")
+    c2w, w2c = camera_matrices(poses)
+    if c2w.shape[0] != depths.shape[0]:
+        raise ValueError(f"{what}: {depths.shape[0]} depth maps for {c2w.shape[0]} poses")
+    k4 = _intrinsics(K, what)
+    voxel_length = float(voxel_length)
+    sdf_trunc = 3.0 * voxel_length if sdf_trunc is None else float(sdf_trunc)
+    depth_trunc, stride = float(depth_trunc), int(stride)
+    inf = float("inf")
+    if not (0.0 < _f32(voxel_length) < inf and 0.0 < _f32(sdf_trunc) < inf and depth_trunc > 0.0):
+        raise ValueError(f"{what}: voxel_length, sdf_trunc and depth_trunc must be positive (and the first two finite)")
+    if stride < 1:
+        raise ValueError(f"{what}: depth_sampling_stride must be at least 1")
+    if depths.shape[0] and (depths.shape[1] < 1 or depths.shape[2] < 1 or depths.shape[1] * depths.shape[2] > 2 ** 31 - 1):
+        raise ValueError(f"{what}: depth maps of shape {tuple(depths.shape[1:])} are not supported")
+    return depths.contiguous(), c2w, w2c, k4, voxel_length, sdf_trunc, min(depth_trunc, 3.0e38), stride
+
+
+def _empty_volume(dev, voxel_length, sdf_trunc):
+    z = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=dev)
+    return TsdfVolume(z(0, 4096), z(0, 4096), z(0, 3, dt=torch.int32), z(0, 0, 0, dt=torch.int32), (0, 0, 0), voxel_length, sdf_trunc)
+
+
+@torch.no_grad()
+def tsdf_integrate(depths: torch.Tensor, poses, K, voxel_length: float = 0.01, sdf_trunc: float = None, depth_trunc: float = 5.0,
+                   depth_sampling_stride: int = 4, _stats=None) -> TsdfVolume:
+    """Fuse device depth maps (n_cam, H, W) into a block-sparse TSDF volume: open3d's ScalableTSDFVolume.integrate for every camera
+    in list order, with the rule written at the head of csrc/tsdf.hip (restated from open3d's sources, not checked against a build of
+    it; open3d also accumulates voxel coordinates incrementally in fp32, which is not imitated).  `sdf_trunc` defaults to
+    3 * voxel_length.  Memory grows with the units the cameras touch (32 KiB each), plus a table of 4-byte unit slots over their
+    bounding box, which may hold at most 2^24 units: a larger extent raises I2SDFError.  Depth maps are read in place (all cameras
+    resident).  Three host synchronisations: the bounding box of the touched units, their number, and the validation word."""
+    depths, c2w, w2c, k4, vl, trunc, dtrunc, stride = _tsdf_args(depths, poses, K, voxel_length, sdf_trunc, depth_trunc,
+                                                                 depth_sampling_stride, "tsdf_integrate")
+    n_cam, H, W = depths.shape
+    dev = depths.device
+    if n_cam == 0:
+        return _empty_volume(dev, vl, trunc)
+    import ctypes as C
+    lib = L.load()
+    ev = _marker(_stats)
+    ul = _f32(16.0 * _f32(vl))
+    K4 = _k4(*k4)
+    i32 = torch.int32
+    with torch.cuda.device(dev):
+        st = L.stream_ptr()
+        c2w_d, w2c_d = c2w.to(dev), w2c.to(dev)
+        big = 2 ** 31 - 1
+        bounds = torch.tensor([big, big, big, -big - 1, -big - 1, -big - 1, 0, 0], dtype=i32, device=dev)
+        ev("start")
+        L.check(lib.i2sdf_tsdf_bounds(L.ptr(depths), n_cam, H, W, L.ptr(c2w_d), K4, vl, ul, trunc, dtrunc, stride, L.ptr(bounds), st),
+                "i2sdf_tsdf_bounds")
+        b = bounds.tolist()
+        if b[6]:
+            raise L.I2SDFError("tsdf_integrate failed (-1): a back-projected point lies beyond 2^20 units of 16 voxels from the origin")
+        if b[0] > b[3]:
+            return _empty_volume(dev, vl, trunc)                  # no measurement in any depth map
+        origin, dims = tuple(b[0:3]), tuple(b[3 + k] - b[k] + 1 for k in range(3))
+        grid6 = (C.c_int32 * 6)(*origin, *dims)
+        cells = int(lib.i2sdf_tsdf_table_cells(grid6))
+        if cells <= 0:
+            raise L.I2SDFError(f"tsdf_integrate failed (-1): the touched units span {dims[0]} x {dims[1]} x {dims[2]} units of 16 voxels; "
+                               f"the unit table holds at most 2^24 cells (voxel_length too small for the extent)")
+        stamp = torch.zeros(cells, dtype=i32, device=dev)
+        flag = torch.zeros(1, dtype=i32, device=dev)
+        L.check(lib.i2sdf_tsdf_mark(L.ptr(depths), n_cam, 0, H, W, L.ptr(c2w_d), K4, vl, ul, trunc, dtrunc, stride, grid6, None, 0,
+                                    L.ptr(stamp), None, None, L.ptr(flag), st), "i2sdf_tsdf_mark")
+        touched = stamp != 0
+        incl = torch.cumsum(touched, 0, dtype=i32)
+        slot = torch.where(touched, incl - 1, torch.full_like(incl, -1))
+        unit_cell = torch.nonzero(touched).reshape(-1).to(i32)   # (synchronises: the number of units sizes the volume)
+        n_units = unit_cell.shape[0]
+        stamp.zero_()
+        tsdf = torch.zeros(n_units, 4096, dtype=torch.float32, device=dev)
+        weight = torch.zeros(n_units, 4096, dtype=torch.float32, device=dev)
+        lst = torch.empty(n_units, dtype=i32, device=dev)
+        counts = torch.zeros(n_cam, dtype=i32, device=dev)
+        for c in range(n_cam):
+            L.check(lib.i2sdf_tsdf_mark(L.ptr(depths), n_cam, c, H, W, L.ptr(c2w_d), K4, vl, ul, trunc, dtrunc, stride, grid6, L.ptr(slot),
+                                        n_units, L.ptr(stamp), L.ptr(lst), L.ptr(counts[c:c + 1]), L.ptr(flag), st), "i2sdf_tsdf_mark")
+            L.check(lib.i2sdf_tsdf_integrate(L.ptr(depths), n_cam, c, H, W, L.ptr(w2c_d), K4, vl, ul, trunc, dtrunc, grid6, L.ptr(unit_cell),
+                                             n_units, L.ptr(lst), L.ptr(counts[c:c + 1]), L.ptr(tsdf), L.ptr(weight), st),
+                    "i2sdf_tsdf_integrate")
+        ev("mark_integrate")
+        if int(flag.item()):
+            raise L.I2SDFError("tsdf_integrate failed (-1): a touched unit lies outside the unit table")
+        uc = unit_cell.to(torch.int64)
+        units = torch.stack([uc // (dims[1] * dims[2]) + origin[0], uc // dims[2] % dims[1] + origin[1], uc % dims[2] + origin[2]], 1).to(i32)
+        if _stats is not None:
+            _stats.append(("touched_units", n_units))
+    return TsdfVolume(tsdf, weight, units, slot.reshape(dims), origin, vl, trunc)
+
+
+@torch.no_grad()
+def tsdf_extract(volume: TsdfVolume, _stats=None) -> Mesh:
+    """The zero-level mesh of a TsdfVolume -- open3d's extract_triangle_mesh by this library's marching cubes: cells of 8 neighbouring
+    voxel centres, across unit borders; a cell counts only if its 8 voxels exist and have weight > 0; a corner is inside iff
+    tsdf < 0; one vertex per crossing lattice edge of a counted cell, at the linear interpolation between the two voxel centres;
+    faces wound so that the right-hand normal points towards positive tsdf (the side the cameras were on), with the fixed rule of
+    csrc/gen_mc_tables.py for ambiguous cells in place of open3d's table.  `normals` are the normalised tsdf central-difference
+    gradient (one-sided where a neighbour is missing), interpolated along the edge, and point towards positive tsdf as well.
+    Vertices come in order of (unit, voxel, axis), not of a hash map.  One host synchronisation reads the two counts."""
+    tsdf, weight, units, slot, origin, vl, _ = volume
+    dev = tsdf.device
+    n_units = tsdf.shape[0]
+    empty = Mesh(torch.empty(0, 3, dtype=torch.float32, device=dev), torch.empty(0, 3, dtype=torch.int32, device=dev),
+                 torch.empty(0, 3, dtype=torch.float32, device=dev))
+    if n_units == 0:
+        return empty
+    import ctypes as C
+    lib = L.load()
+    ev = _marker(_stats)
+    dims = tuple(slot.shape)
+    grid6 = (C.c_int32 * 6)(*origin, *dims)
+    ul = _f32(16.0 * _f32(vl))
+    with torch.cuda.device(dev):
+        st = L.stream_ptr()
+        u = units.to(torch.int64)
+        unit_cell = (((u[:, 0] - origin[0]) * dims[1] + (u[:, 1] - origin[1])) * dims[2] + (u[:, 2] - origin[2])).to(torch.int32)
+        slot_f = slot.contiguous().reshape(-1)
+        nbytes = int(lib.i2sdf_tsdf_extract_workspace_bytes(n_units))
+        if nbytes <= 0 or int(lib.i2sdf_tsdf_table_cells(grid6)) != slot_f.shape[0]:
+            raise ValueError("tsdf_extract: volume not supported")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        blocks = torch.empty(16 * n_units, 2, dtype=torch.int64, device=dev)
+        ev("start")
+        L.check(lib.i2sdf_tsdf_count(grid6, L.ptr(slot_f), L.ptr(unit_cell), n_units, L.ptr(tsdf), L.ptr(weight), L.ptr(ws), L.ptr(blocks), st),
+                "i2sdf_tsdf_count")
+        incl = torch.cumsum(blocks, 0)
+        excl = (incl - blocks).contiguous()
+        n_v, n_f = incl[-1].tolist()
+        if max(n_v, n_f) > 2 ** 31 - 1:
+            raise L.I2SDFError(f"tsdf_extract: {n_v} vertices / {n_f} faces do not fit int32 indices")
+        if n_v == 0 or n_f == 0:
+            return empty
+        verts = torch.empty(n_v, 3, dtype=torch.float32, device=dev)
+        normals = torch.empty(n_v, 3, dtype=torch.float32, device=dev)
+        faces = torch.empty(n_f, 3, dtype=torch.int32, device=dev)
+        L.check(lib.i2sdf_tsdf_emit(grid6, vl, ul, L.ptr(slot_f), L.ptr(unit_cell), n_units, L.ptr(tsdf), L.ptr(weight), L.ptr(ws), L.ptr(excl),
+                                    L.ptr(verts), L.ptr(normals), L.ptr(faces), n_v, n_f, st), "i2sdf_tsdf_emit")
+        ev("extract")
+    return Mesh(verts, faces, normals)
+
+
+@torch.no_grad()
+def tsdf_fuse(depths: torch.Tensor, poses, K, voxel_length: float = 0.01, sdf_trunc: float = None, depth_trunc: float = 5.0,
+              depth_sampling_stride: int = 4, _stats=None) -> Mesh:
+    """tsdf_extract(tsdf_integrate(...)): device depth maps in, the fused surface out (verts, faces, normals on the device).  With
+    the defaults this is utils/mesh_util.py:depth2mesh; refuse() feeds it rendered depth maps.  See the two functions for the rule
+    and for how far it is open3d's."""
+    vol = tsdf_integrate(depths, poses, K, voxel_length, sdf_trunc, depth_trunc, depth_sampling_stride, _stats=_stats)
+    return tsdf_extract(vol, _stats=_stats)
+
+
+@torch.no_grad()
+def refuse(mesh, poses, K, H: int, W: int, far_clip: float = 5.0, _stats=None, **tsdf_kwargs) -> Mesh:
+    """utils/mesh_util.py:refuse on the device: render the mesh's depth from every camera (mesh_depth), fuse the depth maps into a
+    TSDF volume with depth_trunc = far_clip and extract its mesh (tsdf_fuse).  Nothing that no camera sees survives: the outer side
+    of walls, the inside of furniture, whatever lies beyond far_clip.  `tsdf_kwargs`: voxel_length, sdf_trunc, depth_sampling_stride
+    of tsdf_fuse and znear, zfar, cull of mesh_depth.  No mesh, depth map or volume leaves the device.
+    The result is the reference's up to what mesh_depth, tsdf_integrate and tsdf_extract say they do not imitate (the 24-bit depth
+    buffer, open3d's incremental fp32 voxel coordinates, its table for ambiguous cells, its vertex order); neither open3d nor pyrender
+    was available to check the restated rules against."""
+    render = {k: tsdf_kwargs.pop(k) for k in ("znear", "zfar", "cull") if k in tsdf_kwargs}
+    bad = set(tsdf_kwargs) - {"voxel_length", "sdf_trunc", "depth_sampling_stride"}
+    if bad:
+        raise ValueError(f"refuse: unknown arguments {sorted(bad)}")
+    depths = mesh_depth(mesh, poses, K, H, W, _stats=_stats, **render)
+    return tsdf_fuse(depths, poses, K, depth_trunc=far_clip, _stats=_stats, **tsdf_kwargs)
+
+
+@torch.no_grad()
+def score(pred, trgt, poses, K, H: int, W: int, far_clip: float = 5.0, threshold: float = 0.05, down_sample: float = 0.02,
+          **tsdf_kwargs) -> dict:
+    """The three lines of model/eval/recon.py:111-125 on the device:
+        mesh = refuse(pred, poses, K, H, W); gt_mesh = refuse(trgt, poses, K, H, W, far_clip); evaluate(mesh, gt_mesh)
+    -- as in the reference, the prediction is refused with the default far_clip and the target with the given one.  Equal to
+    evaluate(refuse(pred, ...), refuse(trgt, ..., far_clip), threshold, down_sample) exactly; `tsdf_kwargs` go to both refuse calls.
+    The scores are the reference's up to the effects listed under refuse."""
+    p = refuse(pred, poses, K, H, W, **dict(tsdf_kwargs))
+    t = refuse(trgt, poses, K, H, W, far_clip, **dict(tsdf_kwargs))
+    return evaluate(p, t, threshold=threshold, down_sample=down_sample)

@@ -716,6 +716,74 @@ int64_t i2sdf_points_reduce_workspace_bytes(int64_t n);
 int i2sdf_points_threshold_reduce(const float* dist, int64_t n, double threshold, void* workspace, double* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Mesh depth (csrc/raster.hip) -- the depth render of utils/mesh_util.py:refuse (pyrender on EGL in the reference): for every
+ * camera the camera-space z of the nearest triangle along each pixel's ray.  Cameras look along +z with x right and y down
+ * (rend_util.load_K_Rt_from_P); the sample of pixel (column u, row v) is the ray through ((u - cx) / fx, (v - cy) / fy, 1).
+ *   verts (V, 3) fp32, faces (F, 3) int32, device; V, F <= INT32_MAX.  w2c (n_cam, 3, 4) fp32 device: world-to-camera rows.
+ *   K4 = (fx, fy, cx, cy), a HOST array; fx, fy > 0.  H, W >= 1, H W <= INT32_MAX; n_cam <= 65535.  0 < znear <= zfar < inf.
+ *   cull 1: triangles whose right-hand normal points away from the camera (clockwise as the camera sees them) are dropped; 0: kept.
+ *   depth (n_cam, H, W) fp32 <- z of the nearest covered sample with znear <= z <= zfar, 0 where there is none.  Coverage is an
+ *   exact decision (fp64 edge functions, top-left rule: two triangles sharing an edge cover each sample once); samples, not
+ *   triangles, are clipped at znear.  The arithmetic is written out at the head of csrc/raster.hip.  The image does not depend on
+ *   scheduling (a 32-bit integer atomicMin per sample).
+ *   counters (n_cam, 2) int32 <- per camera: triangles rasterised by a workgroup each (pixel box above I2SDF_RASTER_SMALL_MAX
+ *   pixels), triangles rasterised by one lane each.  status: device int32 word, zeroed by the caller; set by a face with a vertex
+ *   index outside [0, V) (such a face is skipped).
+ *   workspace: i2sdf_raster_workspace_bytes(V, F, n_cam) bytes (0: sizes not supported); cameras are processed in chunks that fit
+ *   it.  V = 0, F = 0 or n_cam = 0 enqueue at most the clearing of depth and counters.  Only enqueues; validated on the host first.
+ * ---------------------------------------------------------------------------------------------- */
+#define I2SDF_RASTER_SMALL_MAX 64
+int64_t i2sdf_raster_workspace_bytes(int64_t n_verts, int64_t F, int32_t n_cam);
+int i2sdf_raster_depth(const float* verts, int64_t n_verts, const int32_t* faces, int64_t F, const float* w2c, int32_t n_cam,
+                       const float* K4, int32_t H, int32_t W, float znear, float zfar, int32_t cull, void* workspace, float* depth,
+                       int32_t* counters, int32_t* status, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * TSDF fusion and extraction (csrc/tsdf.hip) -- open3d's ScalableTSDFVolume as utils/mesh_util.py:refuse / :depth2mesh use it
+ * (integrate every depth map, extract_triangle_mesh), restated from its sources; rule and arithmetic at the head of csrc/tsdf.hip.
+ *   depths (n_cam, H, W) fp32 device, a value >= depth_trunc or not > 0 is no measurement; c2w / w2c (n_cam, 3, 4) fp32 device;
+ *   K4 as above (HOST); voxel_length, sdf_trunc, depth_trunc > 0; unit_length = fp32(16 voxel_length), rounded by the caller;
+ *   stride >= 1 (open3d's depth_sampling_stride); n_cam <= 65535.
+ *   grid6 (HOST int32[6]) = lowest touched unit index per axis (|.| <= 2^21), number of units per axis: the dense table of unit
+ *   slots.  i2sdf_tsdf_table_cells(grid6) = its cell count, 0 when a dimension is < 1 or the table would need more than
+ *   I2SDF_TSDF_MAX_CELLS cells (every call that takes grid6 then returns I2SDF_EINVAL).
+ *   _bounds     bounds (device int32[8], set by the caller to INT32_MAX x 3, INT32_MIN x 3, 0, 0) <- min / max unit index touched by
+ *               any camera, bounds[6] <- 1 if a unit index left +-2^20 (that pixel is skipped)
+ *   _mark       slot == NULL: stamp[cell] <- 1 for every cell any camera touches (stamp: device int32 per table cell, zeroed by the
+ *               caller; cell = (ix dims[1] + iy) dims[2] + iz).  The caller turns the stamps into slot[cell] = running count - 1 (-1
+ *               where untouched), unit_cell[slot] = cell, and zeroes them again.  slot != NULL: camera `cam` alone; stamp[cell] <-
+ *               cam + 1, and the slots of the cells it touches are appended to list (n_units) int32, counted in *list_count (device
+ *               int32, zeroed by the caller; cameras must be marked in ascending order).  *flag <- 1 on a cell outside the table.
+ *   _integrate  camera `cam` into the listed units; tsdf, weight: (n_units, 4096) fp32 device, zeroed before the first camera;
+ *               voxel (i, j, k) of a unit at i << 8 | j << 4 | k
+ *   _count      classifies cells and edges; blocks (16 n_units, 2) int64 <- (vertices, faces) of every 256-voxel block.  workspace:
+ *               i2sdf_tsdf_extract_workspace_bytes(n_units) bytes (0 for n_units outside [1, I2SDF_TSDF_MAX_CELLS])
+ *   _emit       blocks_excl = the EXCLUSIVE running sums of `blocks` per column (by the caller, who reads the totals to size the
+ *               outputs); same workspace.  verts / normals (cap_v, 3) fp32, faces (cap_f, 3) int32; rows beyond the capacities are
+ *               not written; cap_v, cap_f <= INT32_MAX.  Vertex order: unit slot, voxel, axis; the right-hand face normal and the
+ *               vertex normals point towards positive tsdf.
+ * Only enqueues; validated on the host first.  Bitwise reproducible from run to run (integer atomics, or the
+ * same constant from every writer as in _mark's union pass; one writer per voxel and per output element).
+ * ---------------------------------------------------------------------------------------------- */
+#define I2SDF_TSDF_MAX_CELLS (1 << 24)
+int64_t i2sdf_tsdf_table_cells(const int32_t* grid6);
+int64_t i2sdf_tsdf_extract_workspace_bytes(int64_t n_units);
+int i2sdf_tsdf_bounds(const float* depths, int32_t n_cam, int32_t H, int32_t W, const float* c2w, const float* K4, float voxel_length,
+                      float unit_length, float sdf_trunc, float depth_trunc, int32_t stride, int32_t* bounds, void* stream);
+int i2sdf_tsdf_mark(const float* depths, int32_t n_cam, int32_t cam, int32_t H, int32_t W, const float* c2w, const float* K4,
+                    float voxel_length, float unit_length, float sdf_trunc, float depth_trunc, int32_t stride, const int32_t* grid6,
+                    const int32_t* slot, int64_t n_units, int32_t* stamp, int32_t* list, int32_t* list_count, int32_t* flag, void* stream);
+int i2sdf_tsdf_integrate(const float* depths, int32_t n_cam, int32_t cam, int32_t H, int32_t W, const float* w2c, const float* K4,
+                         float voxel_length, float unit_length, float sdf_trunc, float depth_trunc, const int32_t* grid6,
+                         const int32_t* unit_cell, int64_t n_units, const int32_t* list, const int32_t* list_count, float* tsdf,
+                         float* weight, void* stream);
+int i2sdf_tsdf_count(const int32_t* grid6, const int32_t* slot, const int32_t* unit_cell, int64_t n_units, const float* tsdf,
+                     const float* weight, void* workspace, int64_t* blocks, void* stream);
+int i2sdf_tsdf_emit(const int32_t* grid6, float voxel_length, float unit_length, const int32_t* slot, const int32_t* unit_cell,
+                    int64_t n_units, const float* tsdf, const float* weight, void* workspace, const int64_t* blocks_excl, float* verts,
+                    float* normals, int32_t* faces, int64_t cap_v, int64_t cap_f, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Bubble-PDF update (row N4) -- VolumeRenderSystem.update_pdf fused with the error it is fed (model/trainer/recon.py:142-152,
  * :195-199 in the initial sweep over all images, :246-252 every training step):
  *   channels == 1: v = |pred - target|                         (criterion DEPTH: depth_values vs depth image)
