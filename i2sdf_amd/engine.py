@@ -552,9 +552,11 @@ class RenderEngine:
         return (bound, ds_out) if want_d_star else bound
 
     # -- full-image inference (N3) ---------------------------------------------------------------
-    def render_image(self, flat_params, uv, pose, intrinsics, chunk, want_normal=True, want_z=False):
+    def render_image(self, flat_params, uv, pose, intrinsics, chunk, want_normal=True, want_z=False, out=None):
         """All chunks of one view in ONE library call (include/i2sdf.h: i2sdf_render_image).  uv (P,2); pose (4,4)|(7); K (4,4).
-        Returns dict(rgb (P,3), depth (P), wsum (P,1), normal (P,3)|None, lmask (P,1)|None, z (P,n_z)|None, iters (n_chunks) int32)."""
+        Returns dict(rgb (P,3), depth (P), wsum (P,1), normal (P,3)|None, lmask (P,1)|None, z (P,n_z)|None, iters (n_chunks) int32).
+        `out`: contiguous fp32 device tensors of those shapes (int32 for iters) to write into instead of new ones, by key -- a view's
+        rows of a stack of views (I2SDFNetwork.evaluate_views)."""
         uv = uv.detach().to(torch.float32).reshape(-1, 2).contiguous()
         pose = pose.detach().to(torch.float32).contiguous()
         intrinsics = intrinsics.detach().to(torch.float32).reshape(4, 4).contiguous()
@@ -572,6 +574,10 @@ class RenderEngine:
         o = {"rgb": e(P, 3), "depth": e(P), "wsum": e(P, 1), "normal": e(P, 3) if want_normal else None,
              "lmask": e(P, 1) if self.cfg.light is not None else None, "z": e(P, self.n_z) if want_z else None,
              "iters": torch.zeros((P + chunk - 1) // chunk, dtype=torch.int32, device=dev)}
+        for k, t in (out or {}).items():
+            if o.get(k) is None or t.shape != o[k].shape or t.dtype != o[k].dtype or t.device != dev or not t.is_contiguous():
+                raise ValueError(f"render_image: out[{k!r}] does not fit (want {None if o.get(k) is None else tuple(o[k].shape)})")
+            o[k] = t.zero_() if k == "iters" else t
         L.check(self._lib.i2sdf_render_image(self._plan, self._pk(), L.ptr(flat_params), C.byref(self._scfg), L.ptr(uv), L.ptr(pose),
                                              int(quat), L.ptr(intrinsics), P, chunk, L.ptr(self.t_lin), L.ptr(self.u_more), L.ptr(self.u_final),
                                              L.ptr(self.extra_tab), L.ptr(ws), L.ptr(o["rgb"]), L.ptr(o["depth"]), L.ptr(o["wsum"]),

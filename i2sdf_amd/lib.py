@@ -78,6 +78,8 @@ MAX_PARTS = 4
 GRID_ORDER_MESHGRID, GRID_ORDER_VOLUME = 0, 1
 RASTER_SMALL_MAX = 64            # I2SDF_RASTER_SMALL_MAX
 TSDF_MAX_CELLS = 1 << 24         # I2SDF_TSDF_MAX_CELLS
+IMAGE_STATS = 8                  # I2SDF_IMAGE_STATS
+SSIM_TILE_X, SSIM_TILE_Y = 32, 16    # I2SDF_SSIM_TILE_X, I2SDF_SSIM_TILE_Y
 
 
 class I2SDFError(RuntimeError):
@@ -200,6 +202,13 @@ SIGNATURES = {
     "i2sdf_tsdf_count": (C.c_int, [_P, _P, _P, _I64, _P, _P, _P, _P, _P]),
     # grid6, voxel_length, unit_length, slot, unit_cell, n_units, tsdf, weight, workspace, blocks_excl, verts, normals, faces, cap_v, cap_f, stream
     "i2sdf_tsdf_emit": (C.c_int, [_P, _F, _F, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _P]),
+    "i2sdf_image_workspace_bytes": (_I64, [_I32, _I32, _I32]),
+    # pred, gt, depth, n_views, H, W, workspace, stats, stream
+    "i2sdf_image_stats": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _P, _P, _P]),
+    # pred, gt, n_views, H, W, data_range, stats, workspace, ssim, map, stream
+    "i2sdf_image_ssim": (C.c_int, [_P, _P, _I32, _I32, _I32, _F, _P, _P, _P, _P, _P]),
+    # rgb, normal, depth, pose, stats, lut, n_views, H, W, rgb8, normal8, normal_cam, depth8, depth_rgb8, stream
+    "i2sdf_image_frames": (C.c_int, [_P] * 6 + [_I32, _I32, _I32] + [_P] * 6),
     # pred, target, channels, pixel_idx, first_pixel, n, pointlinks, n_links, pdf_max, pdf_prune, pdf, n_pdf, n_bad, stream
     "i2sdf_pdf_update": (C.c_int, [_P, _P, _I32, _P, _I64, _I64, _P, _I64, C.c_double, C.c_double, _P, _I64, _P, _P]),
     # seed, B, n_eval, n_samples, n_extra, max_iters, n_z, eik_radius, nbr_half_width, strat_u, cdf_u, extra_idx, eik_idx, eik_pts, nbr_off, stream

@@ -549,6 +549,88 @@ class I2SDFNetwork(nn.Module):
         return out
 
     @torch.no_grad()
+    def evaluate_views(self, poses: torch.Tensor, intrinsics: torch.Tensor, img_res, gt_rgb: Optional[torch.Tensor] = None,
+                       split_n_pixels: int = 12000, frames: bool = False, lut: Optional[torch.Tensor] = None,
+                       keep_outputs: bool = True, _frame_inputs=("rgb", "normal", "depth")) -> Dict[str, torch.Tensor]:
+        """A test sweep with everything on the device: the per-view loop of VolumeRenderSystem.test_step / ViewInterpolateSystem.test_step
+        (model/eval/recon.py:161-203, :257-281) around `render_image`, its metrics and its frames.  `poses` (n, 4, 4) camera-to-world,
+        `intrinsics` (4, 4) or (n, 4, 4), `img_res` (H, W); every view is rendered over i2sdf_amd.views.pixel_grid(H, W) in chunks of
+        `split_n_pixels`, exactly as `render_image` renders it, straight into its rows of (n, H W, C) stacks.
+          gt_rgb (n, H W, 3) on the device: adds "psnr", "ssim" (n,) fp64 (views.image_metrics)
+          frames: adds "rgb8", "normal8", "depth8" (and "depth_rgb8" with a `lut`, a (256, 3) uint8 device tensor) uint8 (n, H, W, C)
+                  (views.to_frames)
+          keep_outputs: adds "rgb_values" (n, H W, 3), "depth_values" (n, H W, 1), "normal_map" (n, H W, 3), "weight_sum" (n, H W, 1).
+                        False: one view's buffers are reused and the metrics / frames are taken view by view (the same numbers).
+        "sampler_iters" (n, n_chunks) int32: the sampler's iteration count per view and chunk.  All results stay on the device;
+        nothing in here waits for it -- the caller's first read of a result is the only host synchronisation."""
+        from . import views as V
+        H, W = V._res(img_res, "evaluate_views", V.SSIM_WINDOW if gt_rgb is not None else 1)
+        hw = H * W
+        dev = next(self.parameters()).device
+        poses = torch.as_tensor(poses).detach().to(dev, torch.float32)
+        if poses.dim() != 3 or tuple(poses.shape[1:]) != (4, 4):
+            raise ValueError(f"evaluate_views: poses must be (n, 4, 4), got {tuple(poses.shape)}")
+        n = poses.shape[0]
+        K = torch.as_tensor(intrinsics).detach().to(dev, torch.float32)
+        K = K.reshape(1, 4, 4).expand(n, 4, 4) if K.dim() == 2 else K
+        if tuple(K.shape) != (n, 4, 4):
+            raise ValueError(f"evaluate_views: intrinsics must be (4, 4) or ({n}, 4, 4), got {tuple(K.shape)}")
+        gt = None if gt_rgb is None else V._stack(gt_rgb, hw, 3, "evaluate_views", "gt_rgb")
+        if gt is not None and gt.shape[0] != n:
+            raise ValueError(f"evaluate_views: {gt.shape[0]} ground-truth images for {n} views")
+        split_n_pixels = int(max(1, min(split_n_pixels, hw)))
+        n_chunks = (hw + split_n_pixels - 1) // split_n_pixels
+        rows = n if keep_outputs else min(n, 1)
+        e = lambda c: torch.empty(rows, hw, c, dtype=torch.float32, device=dev)
+        buf = {"rgb": e(3), "depth": e(1), "wsum": e(1), "normal": e(3)}
+        iters = torch.zeros(n, n_chunks, dtype=torch.int32, device=dev)
+        uv = V.pixel_grid(H, W, dev)
+        eng = self._engine_for(dev)
+        per_view = []
+
+        def finish(sl, lo, hi):
+            r = {}
+            if gt is not None:
+                r.update(V.image_metrics(buf["rgb"][sl], gt[lo:hi], (H, W)))
+            if frames:
+                src = {k: buf[k][sl] if k in _frame_inputs else None for k in ("rgb", "normal", "depth")}
+                r.update(V.to_frames(rgb=src["rgb"], normal_map=src["normal"], depth=src["depth"], pose=poses[lo:hi], img_res=(H, W),
+                                     lut=lut))
+            return r
+
+        with torch.cuda.device(dev):
+            for i in range(n):
+                j = i if keep_outputs else 0
+                eng.render_image(self._flat, uv[0], poses[i], K[i], split_n_pixels,
+                                 out={"rgb": buf["rgb"][j], "depth": buf["depth"][j, :, 0], "wsum": buf["wsum"][j], "normal": buf["normal"][j],
+                                      "iters": iters[i]})
+                if not keep_outputs:
+                    per_view.append(finish(slice(0, 1), i, i + 1))
+        out = {"sampler_iters": iters}
+        if keep_outputs:
+            out.update(finish(slice(0, n), 0, n))
+            out.update({"rgb_values": buf["rgb"], "depth_values": buf["depth"], "normal_map": buf["normal"], "weight_sum": buf["wsum"]})
+        elif per_view:
+            out.update({k: torch.cat([r[k] for r in per_view], 0) for k in per_view[0]})
+        return out
+
+    @torch.no_grad()
+    def render_path(self, pose0, pose1, intrinsics, img_res, num_frames: int = 60, use_normal: bool = True,
+                    split_n_pixels: int = 12000) -> Dict[str, torch.Tensor]:
+        """The frames of a view interpolation (ViewInterpolateSystem, model/eval/recon.py:227-281): the camera path of
+        views.interpolate_poses between two camera-to-world poses, rendered by evaluate_views.  Returns "poses" (num_frames, 4, 4) fp32
+        on the device, "rgb8" and (use_normal) "normal8" uint8 (num_frames, H, W, 3), "sampler_iters".  Writing the images and the
+        video is the caller's."""
+        from . import views as V
+        poses = V.interpolate_poses(pose0, pose1, num_frames)
+        o = self.evaluate_views(poses, intrinsics, img_res, split_n_pixels=split_n_pixels, frames=True, keep_outputs=False,
+                                _frame_inputs=("rgb", "normal") if use_normal else ("rgb",))
+        out = {"poses": poses.to(o["sampler_iters"].device), "rgb8": o["rgb8"], "sampler_iters": o["sampler_iters"]}
+        if use_normal:
+            out["normal8"] = o["normal8"]
+        return out
+
+    @torch.no_grad()
     def sdf_grid(self, points: torch.Tensor, chunk: int = 1 << 20) -> torch.Tensor:
         """SDF values of an arbitrary point set in chunks (marching-cubes grids: model/eval/recon.py:46-51,89-90,
         utils/plots.py:440-489).  Returns (M,)."""

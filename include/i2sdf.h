@@ -784,6 +784,52 @@ int i2sdf_tsdf_emit(const int32_t* grid6, float voxel_length, float unit_length,
                     float* normals, int32_t* faces, int64_t cap_v, int64_t cap_f, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Rendered views (csrc/imgops.hip) -- what model/eval/recon.py does with a finished view (VolumeRenderSystem.test_step :161-203,
+ * ViewInterpolateSystem.test_step :257-281): PSNR, SSIM, the camera-space normal map and the 8-bit frames given to the image writers.
+ * Images have the render outputs' layout: pixel-major, channel-last fp32, (n_views, H W, C) contiguous, pixel p = y W + x, C = 3 for
+ * rgb and normals and 1 for depth.  n_views <= 65535, H, W >= 1 (>= 11 for _ssim), H W <= INT32_MAX, else I2SDF_EINVAL; n_views = 0
+ * returns I2SDF_OK and writes nothing.  workspace: i2sdf_image_workspace_bytes(n_views, H, W) bytes (0: sizes not supported), shared
+ * by _stats and _ssim (disjoint parts).  Only enqueues; validated on the host first; no allocation.  Bitwise reproducible from run to
+ * run: workgroups write fixed slots of the workspace that a second kernel adds in a fixed order (no floating-point atomics).
+ *   _stats   stats (n_views, I2SDF_IMAGE_STATS) fp64 device <- per view
+ *              [0] sum over the 3 H W values of ((double)pred - (double)gt)^2     (mse = [0] / (3 H W), psnr = -10 log10(mse):
+ *                  utils/rend_util.py:get_psnr, which takes the mean in fp32)
+ *              [1], [2] min, max of pred   [3], [4] min, max of gt   [5] max of depth   [6], [7] 0
+ *            pred and gt (n_views, H W, 3) are given together or both NULL ([0] = 0, [1..4] = +inf, -inf, +inf, -inf); depth
+ *            (n_views, H W) may be NULL ([5] = -inf); one of the two groups must be there.  NaNs are passed over by min / max.
+ *   _ssim    ssim (n_views) fp64 device <- torchmetrics 0.11.4 structural_similarity_index_measure with its defaults (Gaussian
+ *            window of 11 taps, sigma 1.5, k1 0.01, k2 0.03), restated from its source:
+ *              g[i] = exp(-((i - 5) / 1.5)^2 / 2) / sum;  E[.] = the separable window mean, per channel;
+ *              s_p = E[pp] - E[p]^2, s_t = E[tt] - E[t]^2, s_pt = E[pt] - E[p] E[t], c1 = (0.01 R)^2, c2 = (0.03 R)^2,
+ *              ssim = ((2 E[p] E[t] + c1) (2 s_pt + c2)) / ((E[p]^2 + E[t]^2 + c1) (s_p + s_t + c2)),
+ *            averaged over the 3 channels and the (H - 10) x (W - 10) pixels whose window lies inside the image (torchmetrics
+ *            reflect-pads by 5 and crops 5 from the result: the same pixels).  R = data_range, finite and > 0; or NaN for
+ *            max(max p - min p, max t - min t) of the view, read on the device from `stats` as _stats left it for the same pred, gt
+ *            (torchmetrics' data_range=None for a batch of one view).  Moments in fp32 (as the reference's convolution), each
+ *            product and sum rounded on its own; the per-pixel values are added in fp64.  One workgroup per
+ *            I2SDF_SSIM_TILE_Y x I2SDF_SSIM_TILE_X tile of the result.
+ *            map: NULL, or (n_views, H - 10, W - 10, 3) fp32 <- the per-pixel values; ssim is bit-identical either way.
+ *   _frames  uint8 images (n_views, H, W, C); every output may be NULL (not written):
+ *              rgb8       = trunc(clip(rgb * 255, 0, 255))                                     needs rgb
+ *              normal_cam = pose[:3, :3]^T n  (summed in fp64, rounded to fp32 once; (n_views, H W, 3));  normal8 = trunc(clip((normal_cam + 1) / 2 * 255, 0, 255))
+ *                           needs normal (world space) and pose (n_views, 4, 4) fp32 device, camera-to-world
+ *              depth8     = trunc(clip(d / (stats[view][5] + 1e-6f) * 255, 0, 255))            needs depth and stats (_stats with depth)
+ *              depth_rgb8 = lut[depth8], lut (256, 3) uint8 device: the caller's colour map    needs depth, stats and lut
+ *            A NaN becomes 0.
+ * ---------------------------------------------------------------------------------------------- */
+#define I2SDF_IMAGE_STATS 8
+#define I2SDF_SSIM_TILE_X 32
+#define I2SDF_SSIM_TILE_Y 16
+int64_t i2sdf_image_workspace_bytes(int32_t n_views, int32_t H, int32_t W);
+int i2sdf_image_stats(const float* pred, const float* gt, const float* depth, int32_t n_views, int32_t H, int32_t W, void* workspace,
+                      double* stats, void* stream);
+int i2sdf_image_ssim(const float* pred, const float* gt, int32_t n_views, int32_t H, int32_t W, float data_range, const double* stats,
+                     void* workspace, double* ssim, float* map, void* stream);
+int i2sdf_image_frames(const float* rgb, const float* normal, const float* depth, const float* pose, const double* stats,
+                       const uint8_t* lut, int32_t n_views, int32_t H, int32_t W, uint8_t* rgb8, uint8_t* normal8, float* normal_cam,
+                       uint8_t* depth8, uint8_t* depth_rgb8, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Bubble-PDF update (row N4) -- VolumeRenderSystem.update_pdf fused with the error it is fed (model/trainer/recon.py:142-152,
  * :195-199 in the initial sweep over all images, :246-252 every training step):
  *   channels == 1: v = |pred - target|                         (criterion DEPTH: depth_values vs depth image)
