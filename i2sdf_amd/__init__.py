@@ -17,9 +17,9 @@ def __getattr__(name):
     if name == "FusedAdam":
         from .optim import FusedAdam
         return FusedAdam
-    if name == "BubblePDF":
-        from .bubble import BubblePDF
-        return BubblePDF
+    if name in ("BubblePDF", "depth_unproject"):
+        from . import bubble
+        return getattr(bubble, name)
     if name in ("GridAxes", "uniform_axes", "aligned_axes", "pca_frame"):
         from . import grid
         return getattr(grid, name)

@@ -9,23 +9,16 @@
 // rejection (k = 32 of n >= 128: exactly uniform, in random order, ~1.1 draws per element).
 #include <hip/hip_runtime.h>
 #include "../../include/i2sdf.h"
+#include "philox.h"
 
 int i2sdf_hip_check(hipError_t e, const char* what);
 
 namespace {
 
-struct U4 { unsigned x, y, z, w; };
+using i2sdf_philox::U4;
+using i2sdf_philox::philox4x32_10;
 constexpr int MAX_EXTRA_ROWS = 16, MAX_EXTRA = 128;      // sampler iterations / extra columns the k-subset thread supports
 
-__device__ __forceinline__ U4 philox4x32_10(U4 c, unsigned k0, unsigned k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned long long p0 = 0xD2511F53ull * c.x, p1 = 0xCD9E8D57ull * c.z;
-    c = U4{(unsigned)(p1 >> 32) ^ c.y ^ k0, (unsigned)p1, (unsigned)(p0 >> 32) ^ c.w ^ k1, (unsigned)p0};
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  return c;
-}
 __device__ __forceinline__ float u01(unsigned x) { return (float)(x >> 8) * 5.9604644775390625e-8f; }   // [0, 1), 24 bits like torch.rand
 
 struct DrawArgs {

@@ -80,6 +80,8 @@ RASTER_SMALL_MAX = 64            # I2SDF_RASTER_SMALL_MAX
 TSDF_MAX_CELLS = 1 << 24         # I2SDF_TSDF_MAX_CELLS
 IMAGE_STATS = 8                  # I2SDF_IMAGE_STATS
 SSIM_TILE_X, SSIM_TILE_Y = 32, 16    # I2SDF_SSIM_TILE_X, I2SDF_SSIM_TILE_Y
+BUBBLE_MAX_K = 4096              # I2SDF_BUBBLE_MAX_K
+BUBBLE_WS_PASSES_OFFSET = 24     # I2SDF_BUBBLE_WS_PASSES_OFFSET
 
 
 class I2SDFError(RuntimeError):
@@ -213,6 +215,16 @@ SIGNATURES = {
     "i2sdf_pdf_update": (C.c_int, [_P, _P, _I32, _P, _I64, _I64, _P, _I64, C.c_double, C.c_double, _P, _I64, _P, _P]),
     # seed, B, n_eval, n_samples, n_extra, max_iters, n_z, eik_radius, nbr_half_width, strat_u, cdf_u, extra_idx, eik_idx, eik_pts, nbr_off, stream
     "i2sdf_training_draws": (C.c_int, [C.c_uint64, _I64, _I32, _I32, _I32, _I32, _I32, C.c_float, C.c_float, _P, _P, _P, _P, _P, _P, _P]),
+    "i2sdf_bubble_sample_workspace_bytes": (_I64, [_I64]),
+    # weights, n, pointcloud, k, seed, draw, workspace, idx, points, sample_count, status, stream
+    "i2sdf_bubble_sample": (C.c_int, [_P, _I64, _P, _I64, C.c_uint64, C.c_uint32, _P, _P, _P, _P, _P, _P]),
+    # weights, n, seed, draw, keys_out, stream
+    "i2sdf_bubble_keys": (C.c_int, [_P, _I64, C.c_uint64, C.c_uint32, _P, _P]),
+    "i2sdf_depth_unproject_workspace_bytes": (_I64, [_I64, _I32, _I32]),
+    # depth, n_img, H, W, lo, hi, workspace, depth_masks, n_points (host), stream
+    "i2sdf_depth_unproject_count": (C.c_int, [_P, _I64, _I32, _I32, _F, _F, _P, _P, C.POINTER(_I64), _P]),
+    # depth, intrinsics, pose, n_img, H, W, lo, hi, workspace, n_points, pointlinks, pixlinks, pointcloud, stream
+    "i2sdf_depth_unproject_write": (C.c_int, [_P, _P, _P, _I64, _I32, _I32, _F, _F, _P, _I64, _P, _P, _P, _P]),
     "i2sdf_light_forward": (C.c_int, [_P, _P, _P, _I64, _I64, _P, _P, _P]),
     "i2sdf_light_backward": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _P, _P, _P]),
     "i2sdf_loss_scratch_floats": (_I64, []),

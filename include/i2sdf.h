@@ -856,6 +856,71 @@ int i2sdf_training_draws(uint64_t seed, int64_t B, int32_t n_eval, int32_t n_sam
                          int32_t n_z, float eik_radius, float nbr_half_width, float* strat_u, float* cdf_u,
                          int32_t* extra_idx, int32_t* eik_idx, float* eik_pts, float* nbr_off, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Bubble points drawn by the PDF on the device (row N4) -- VolumeRenderSystem.sample_bubble (model/trainer/recon.py:154-170)
+ * without its blocking torch.where and without torch.multinomial's 2^24 category limit: k of n entries without replacement,
+ * proportional to `weights`, in one stream-ordered call (no allocation, no synchronisation, no host read).
+ *
+ * Law: successive sampling (the law of torch.multinomial(replacement=False), a different random stream).
+ *   entry i is eligible iff 0 < weights[i] < inf (NaN, negative, zero and infinite entries are not); weights == NULL: every weight
+ *   is 1 (the uniform_bubble ablation, randperm(n)[:k] without n indices);
+ *   key_i = min(E_i / weights[i], FLT_MAX) in fp32 (the clamp keeps an eligible entry in front of every not-eligible one when the
+ *           quotient overflows);  E_i = -log1pf(-v_i);  v_i = ((float)x_i + 0.5f) * 2^-32  (fp32 operations; the small end of E,
+ *           which is where the k smallest keys of many entries lie, keeps all 32 random bits);
+ *   x_i   = word (i & 3) of Philox4x32-10 with counter (lo32(i >> 2), hi32(i >> 2), 7, draw) and key (lo32(seed), hi32(seed)):
+ *           one Philox call per four neighbouring entries = one 16-byte load of `weights`;  `draw`: the caller's call counter;
+ *   result: the k eligible entries with the smallest composite (bits(key_i), i), in ascending order of the composite -- the order
+ *           of the successive draws; ties on the key go to the lower index.
+ * Outputs: idx (k) int64;  points (k, 3) = pointcloud[idx] (pointcloud == NULL or points == NULL: skipped);
+ *   sample_count[idx] += 1 (fp32, n entries; NULL: skipped -- the indices are distinct, no atomics).
+ * Shortfall: with only m < k eligible entries rows [0, m) are the draw and row j >= m repeats row j mod m; sample_count counts the m
+ *   real draws; m = 0: idx = -1, points = 0.  *status (device int32, or NULL) accumulates k - m.  If so many keys EQUAL the k-th
+ *   smallest that more than 2k entries have key <= it (collisions of 2^-32), the first k of the 2k captured are returned and
+ *   *status grows by 1; nothing is written out of bounds.  The host never reads m.
+ * Limits (checked on the host before any launch, I2SDF_EINVAL): 1 <= k <= I2SDF_BUBBLE_MAX_K, 0 <= n < 2^31, idx and workspace
+ *   not NULL.  workspace: i2sdf_bubble_sample_workspace_bytes(k) bytes (0 for a k outside the limits), 16-byte aligned; the call
+ *   clears what it needs on `stream`.
+ * Method: an exact radix select over the key bits (12 + 10 + 9; bit 31 is 0): per-workgroup LDS histograms merged by integer atomics
+ *   (order-independent, so the result is bitwise reproducible), a one-wave pick of the bin where the running count crosses k, then a
+ *   collect of every key <= the threshold and one workgroup that sorts those by the composite.  The threshold is the upper end of
+ *   the first chosen bin with at most 2k entries at or below it -- the later histogram passes then return at once; keys near the
+ *   small end are evenly spread, so pass A alone decides unless the keys cluster -- and the k-th smallest key itself after pass C.
+ *   The keys are recomputed from (i, weights[i]) in every pass and never stored: 4 n bytes are read per pass, 2 to 4 passes
+ *   (1 to 3 histogram passes and the collect pass).  How many a call made is left in its workspace, for measurements: the uint32
+ *   at byte I2SDF_BUBBLE_WS_PASSES_OFFSET, valid once the call has completed on `stream` and until the next call on that workspace.
+ * i2sdf_bubble_keys: the fp32 keys themselves (keys_out (n); +inf for a not-eligible entry) from the device function the select uses.
+ * ---------------------------------------------------------------------------------------------- */
+#define I2SDF_BUBBLE_MAX_K 4096
+#define I2SDF_BUBBLE_WS_PASSES_OFFSET 24
+int64_t i2sdf_bubble_sample_workspace_bytes(int64_t k);
+int i2sdf_bubble_sample(const float* weights, int64_t n, const float* pointcloud, int64_t k, uint64_t seed, uint32_t draw,
+                        void* workspace, int64_t* idx, float* points, float* sample_count, int32_t* status, void* stream);
+int i2sdf_bubble_keys(const float* weights, int64_t n, uint64_t seed, uint32_t draw, float* keys_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Point cloud and pixel <-> point links from the depth maps (dataset/train_dataset.py:112-141, utils/rend_util.py:81-89,134-147),
+ * a stream compaction in the reference's order (image-major, pixel order within an image):
+ *   depth (n_img, H W) fp32, intrinsics (n_img, 4, 4), pose (n_img, 4, 4) camera-to-world, all device;
+ *   pixel p of an image: u = p mod W, v = p div W;  valid iff lo < d < hi (a NaN is not; the reference: lo = 1e-3, hi = 6);
+ *   x_l = (u - cx + cy sk / fy - sk v / fy) / fx,  y_l = (v - cy) / fy   (fx = K00, fy = K11, cx = K02, cy = K12, sk = K01);
+ *   point = (pose [x_l d, y_l d, d, 1]^T)[:3] / its fourth component.
+ *   _count: depth_masks (n_img H W) bytes 0 / 1 (or NULL) and the per-block counts and their exclusive scan in `workspace`
+ *           (i2sdf_depth_unproject_workspace_bytes(n_img, H, W) bytes; 0 for sizes outside the limits); n_points (HOST int64) is
+ *           copied back -- ONE stream synchronisation: this is set-up, the caller sizes the outputs with it.
+ *   _write: same inputs and workspace; pointlinks (n_img H W) int64, -1 where the pixel is not valid; pixlinks (n_points) int64
+ *           global pixel index; pointcloud (n_points, 3).  n_points: what _count returned (writes past it are dropped).
+ * Limits (I2SDF_EINVAL): n_img >= 0, H, W >= 1, H W <= INT32_MAX, n_img H W < 2^36; n_img = 0 is a no-op with n_points = 0.
+ * Cost: the per-block counts (one per 1024 pixels) are scanned by ONE workgroup, 256 counts per round with three barriers a round:
+ *   180 rounds for the reference's 150 views of 640 x 480 (45 000 blocks), but 262 144 serial rounds at the 2^36 limit -- the limit
+ *   is what the indices allow, not a size at which this set-up call is quick.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t i2sdf_depth_unproject_workspace_bytes(int64_t n_img, int32_t H, int32_t W);
+int i2sdf_depth_unproject_count(const float* depth, int64_t n_img, int32_t H, int32_t W, float lo, float hi, void* workspace,
+                                uint8_t* depth_masks, int64_t* n_points, void* stream);
+int i2sdf_depth_unproject_write(const float* depth, const float* intrinsics, const float* pose, int64_t n_img, int32_t H, int32_t W,
+                                float lo, float hi, const void* workspace, int64_t n_points, int64_t* pointlinks, int64_t* pixlinks,
+                                float* pointcloud, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
