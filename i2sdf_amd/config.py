@@ -36,7 +36,10 @@ class MlpShape:
 
     @property
     def pe_dim(self):
-        return self.d_in + 2 * self.d_in * self.multires if self.multires > 0 else self.d_in
+        """width of the encoded input in front of the hidden / feature columns of layer 0 (csrc/plan.h: side_dim); a radiance net in 'idr'
+        mode (d_in 9) encodes only the view direction: [x | PE(view) | normal]"""
+        raw = 3 if self.d_in == 9 else self.d_in
+        return (raw + 2 * raw * self.multires if self.multires > 0 else raw) + (self.d_in - raw)
 
 
 @dataclass
@@ -117,13 +120,20 @@ class NetConfig:
         sdf = MlpShape("implicit_network", dims, hid[0], d_in, multires, skip_in[0] if skip_in else -1)
         # --- RenderingNetwork (mlp.py:176-198)
         mode = _get(rnet, "mode")
-        if mode != "nerf":
-            raise NotImplementedError("rendering_network.mode must be 'nerf' (the shipped configs)")
+        if mode not in ("nerf", "idr"):
+            raise NotImplementedError("rendering_network.mode must be 'nerf' (the shipped configs) or 'idr' (their documented two-line switch)")
+        if mode == "idr" and _get(rnet, "embed_point", None) is not None:
+            raise NotImplementedError("rendering_network.embed_point: the reference builds that embedder and widens lin0 for it, but never "
+                                      "applies it in forward() (model/network/mlp.py:185-190, 208-216: the raw points are concatenated), so the "
+                                      "option cannot run there either")
         mr_v = int(_get(rnet, "multires", 0)) if _get(rnet, "embed_type", None) else 0
         rhid = list(_get(rnet, "dims"))
-        r_in = int(_get(rnet, "d_in")) + fvs + (6 * mr_v if mr_v else 0)
+        r_d_in = int(_get(rnet, "d_in"))
+        if mode == "idr" and r_d_in != 9:
+            raise NotImplementedError(f"rendering_network.d_in must be 9 (points, view directions, normals) in 'idr' mode; got {r_d_in}")
+        r_in = r_d_in + fvs + (6 * mr_v if mr_v else 0)
         rfull = [r_in] + rhid + [int(_get(rnet, "d_out"))]
-        rgb = MlpShape("rendering_network", [(rfull[l + 1], rfull[l]) for l in range(len(rfull) - 1)], rhid[0], 3, mr_v)
+        rgb = MlpShape("rendering_network", [(rfull[l + 1], rfull[l]) for l in range(len(rfull) - 1)], rhid[0], 9 if mode == "idr" else 3, mr_v)
         light = None
         if _has(conf, "light_network"):
             lhid = list(_get(_get(conf, "light_network"), "dims"))
@@ -157,7 +167,7 @@ class NetConfig:
                          scene_bounding_sphere=float(_get(conf, "scene_bounding_sphere", 1.0)),
                          beta_init=float(_get(_get(dens, "params_init"), "beta")), beta_min=float(_get(dens, "beta_min", 1e-4)),
                          sdf_bias=float(_get(inet, "bias", 1.0)), use_normal=bool(_get(conf, "use_normal", False)),
-                         detach_light_feature=bool(_get(conf, "detach_light_feature", True)),
+                         detach_light_feature=bool(_get(conf, "detach_light_feature", True)), rgb_mode=mode,
                          bf16x3=bool(_get(conf, "bf16x3", True)), wgrad_bf16x2=bool(_get(conf, "wgrad_bf16x2", True)),
                          sampler_bf16x2=bool(_get(conf, "sampler_bf16x2", True)), saves24=bool(_get(conf, "saves24", True)))
 

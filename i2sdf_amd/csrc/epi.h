@@ -77,6 +77,22 @@ struct StoreEpi {
   }
   I2SDF_APPLY_FROM_ELEM
 };
+// radiance backward, 'idr' mode: tiles < FT are the feature gradient (plain store); tile FT holds W_0[:, normal columns]^T G(a_0) in its
+// rows 0..2 (registers 0..2 of the lanes with hi == 0) -> nbar (3 floats of this lane's point), written or added
+template <int FT>
+struct StoreNbarEpi {
+  float* row; float* nrow; int add; int hi; bool valid;
+  __device__ __forceinline__ void prefetch(int) {}
+  __device__ __forceinline__ void elem(int nt, f32x16& acc, int r) {
+    if (nt < FT) {
+      if ((r & 3) == 3) store_quad(row, nt, r >> 2, hi, valid, acc);
+    } else if (r == 3 && hi == 0 && valid) {
+#pragma unroll
+      for (int j = 0; j < 3; ++j) nrow[j] = add ? nrow[j] + acc[j] : acc[j];
+    }
+  }
+  I2SDF_APPLY_FROM_ELEM
+};
 
 // d sdf/dx chain: abar_{l-1} = (W_l^T abar_l) * scale * sigma(h_l) [store]; tiles >= NT (skip layer) add into pbar
 template <int NT, int PT, bool PRE>

@@ -50,6 +50,9 @@ struct RgbFwdArgs {
   float* pev_save;                      // (Mp, PECV*8) PE(view dir), or nullptr
   int kcs = 16;                         // layout of rs for the points of this launch
   int wg0 = 0;                          // first 128-point workgroup of this launch
+  // 'idr' mode only (include/i2sdf.h: i2sdf_rgb_forward_idr): the side row is [x | PE(view) | normal], pev_save is (Mp, 40)
+  i2sdf::PointSpec pts{};               // x of point m
+  const float* normals = nullptr;       // (M,3) d sdf/dx as i2sdf_sdf_forward_grad returned it
 };
 
 struct RgbBwdArgs {
@@ -63,6 +66,9 @@ struct RgbBwdArgs {
   float* fbar;              // (Mp, F)
   int kcs = 16;             // layout of rs / gar for the points of this launch
   int wg0 = 0;              // first 128-point workgroup of this launch
+  // 'idr' mode only (i2sdf_rgb_backward_idr): d loss / d normal = W_0[:, normal columns]^T G(a_0)
+  float* nbar = nullptr;    // (M,3)
+  int nbar_acc = 0;         // 0: written, 1: added to what is there
 };
 
 // bf16x3 kernels: launch over `grid` workgroups of 128 points -- four 32-point waves (mlp_x3.hip: d sdf/dx chain, sweeps) or eight 16-point
@@ -72,6 +78,8 @@ void i2sdf_launch_sdf_bwd3(const SdfBwdArgs& a, unsigned grid, hipStream_t st);
 void i2sdf_launch_train_fwd3h(const SdfTrainFwdArgs& a, unsigned grid, hipStream_t st);
 void i2sdf_launch_rgb_fwd3h(const RgbFwdArgs& a, unsigned grid, hipStream_t st);
 void i2sdf_launch_rgb_bwd3h(const RgbBwdArgs& a, unsigned grid, hipStream_t st);
+void i2sdf_launch_rgb_fwd3h_idr(const RgbFwdArgs& a, int view_multires, unsigned grid, hipStream_t st);      // 4 or 0
+void i2sdf_launch_rgb_bwd3h_idr(const RgbBwdArgs& a, unsigned grid, hipStream_t st);
 // light-mask head forward on 16-point waves (mlp_x3h.hip): lm = sigmoid(W1 softplus100(W0 relu(feature) + b0) + b1), hl = the softplus activations
 struct LightFwd3hArgs {
   const float* fwd; int n_fwd;

@@ -220,7 +220,8 @@ __global__ __launch_bounds__(256) void sdf_bwd_split_kernel(SdfBwdArgs a, int64_
 
 namespace {
 
-template <int H, int F>
+// IDR: the last reverse product runs one more tile, the three normal rows of W_0^T (plan.cpp: build_rgb) -> nbar
+template <int H, int F, bool IDR = false>
 __global__ __launch_bounds__(256) void rgb_bwd_kernel(RgbBwdArgs a) {
   constexpr int NT = H / 32, KC = H / 8, FT = F / 32;
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -283,7 +284,11 @@ __global__ __launch_bounds__(256) void rgb_bwd_kernel(RgbBwdArgs a) {
     dense_op_epi<NT, KC, 0, 1, 0, MaskEpi<PRE>>(ws, ga, acc, e, tid);
     commit_tiles<NT>(acc, ga);
   }
-  {
+  if constexpr (IDR) {
+    f32x16 fa[FT + 1];
+    StoreNbarEpi<FT> se{a.fbar + m * F, a.nbar + m * 3, a.nbar_acc, hi, valid};
+    dense_op_epi<FT + 1, KC, 0, 1, 0, StoreNbarEpi<FT>>(ws, ga, fa, se, tid);
+  } else {
     f32x16 fa[FT];
     StoreEpi se{a.fbar + m * F, hi, valid};
     dense_op_epi<FT, KC, 0, 1, 0, StoreEpi>(ws, ga, fa, se, tid);
@@ -410,6 +415,7 @@ extern "C" int i2sdf_rgb_backward(const i2sdf_plan* p, const float* packed, cons
   if (!p || !packed || !rgb || !rgb_bar || !rs || !gar || !ga_last || !fbar || M < 0) return I2SDF_EINVAL;
   if (Mp < M || Mp % PTS_PER_WG) return I2SDF_EINVAL;
   const i2sdf_mlp_desc& d = p->rgb.d;
+  if (rgb_idr(d)) return I2SDF_EINVAL;                  // ('idr' plans: i2sdf_rgb_backward_idr)
   const bool wide = d.hidden == 256 && p->F == 256, x3 = wide && p->rgb_bf16x3;
   if (!wide && !(d.hidden == 64 && p->F == 64)) return I2SDF_EINVAL;
   const Span rev = span(p, packed, p->rgb, SPAN_REV);
@@ -439,4 +445,36 @@ extern "C" int i2sdf_rgb_backward(const i2sdf_plan* p, const float* packed, cons
   if (wide) i2sdf_dispatch_points(p, st, M, ranged, true, TAIL_BEHIND, full, tail);
   else launch_lds(rgb_bwd_kernel<64, 64>, (unsigned)((M + PTS_PER_WG - 1) / PTS_PER_WG), st, a);
   return i2sdf_hip_check(hipGetLastError(), "rgb_backward launch");
+}
+
+// 'idr' mode (include/i2sdf.h): the same launches over the kernels' IDR instantiations, full workgroups only (as i2sdf_rgb_forward_idr)
+extern "C" int i2sdf_rgb_backward_idr(const i2sdf_plan* p, const float* packed, const float* rgb, const float* rgb_bar, const float* rs,
+                                      int64_t M, int64_t Mp, float* gar, float* ga_last, float* fbar, float* nbar, int32_t accumulate,
+                                      void* stream) {
+  if (M == 0) return I2SDF_OK;                 // empty batch: nothing to validate, nothing to launch
+  if (!p || !packed || !rgb || !rgb_bar || !rs || !gar || !ga_last || !fbar || !nbar || M < 0) return I2SDF_EINVAL;
+  if (Mp < M || Mp % PTS_PER_WG) return I2SDF_EINVAL;
+  const i2sdf_mlp_desc& d = p->rgb.d;
+  if (!rgb_idr(d)) return I2SDF_EINVAL;
+  const bool wide = d.hidden == 256 && p->F == 256, x3 = wide && p->rgb_bf16x3;
+  if (!wide && !(d.hidden == 64 && p->F == 64)) return I2SDF_EINVAL;
+  const Span rev = span(p, packed, p->rgb, x3 ? SPAN_REV3H : SPAN_REV);
+  if (!rev.n_stages) return I2SDF_EINVAL;
+  RgbBwdArgs a{};
+  a.rev = rev.w; a.n_rev = rev.n_stages;
+  a.L = d.n_lin; a.M = M; a.Mp = Mp; a.rgb = rgb; a.rgb_bar = rgb_bar; a.rs = rs; a.gar = gar; a.ga_last = ga_last; a.fbar = fbar;
+  a.nbar = nbar; a.nbar_acc = accumulate ? 1 : 0;
+  if (x3) a.kcs = rgb_blocked_points(p, M, Mp) > 0 ? KCS_BLK : KCS_PM;
+  hipStream_t st = (hipStream_t)stream;
+  const bool ranged = x3 && i2sdf_parts_on(p);
+  ChainGuard guard(p, st, ranged);
+  auto full = [&](hipStream_t s, int wg0, unsigned g, int64_t Mv) {
+    RgbBwdArgs x = a;
+    x.wg0 = wg0; x.M = Mv;
+    if (x3) i2sdf_launch_rgb_bwd3h_idr(x, g, s);
+    else if (wide) launch_lds(rgb_bwd_kernel<256, 256, true>, g, s, x);
+    else launch_lds(rgb_bwd_kernel<64, 64, true>, g, s, x);
+  };
+  i2sdf_dispatch_points(p, st, M, ranged, false, TAIL_BEHIND, full, [](hipStream_t, int64_t) {});
+  return i2sdf_hip_check(hipGetLastError(), "rgb_backward_idr launch");
 }

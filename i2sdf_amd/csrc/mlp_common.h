@@ -71,7 +71,7 @@ inline bool sdf_saves24(const i2sdf_plan* p) {
 }
 inline int64_t rgb_blocked_points(const i2sdf_plan* p, int64_t M, int64_t Mp) {
   if (!p->blocked_saves || !p->rgb_bf16x3 || p->rgb.d.hidden != 256 || p->F != 256) return 0;
-  if (i2sdf_parts_on(p)) return Mp;
+  if (i2sdf_parts_on(p) || i2sdf::rgb_idr(p->rgb.d)) return Mp;      // ('idr' mode: no split-K tail either, i2sdf_rgb_forward_idr)
   const int64_t bulk = split_bulk_points(M, p->n_cu);
   return bulk > 0 ? bulk : Mp;
 }

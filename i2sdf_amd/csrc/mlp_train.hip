@@ -3,7 +3,7 @@
 //                   reference builds d sdf/dx with torch.autograd.grad(create_graph=True); here the reverse chain
 //                    is evaluated explicitly in the same kernel, in registers.
 //                   Saves h_l = softplus(a_{l-1}) and abar_l = d sdf / d a_l for the backward kernels.
-//   rgb_fwd       : RenderingNetwork.forward, 'nerf' mode (mlp.py:208-229), saves the post-ReLU activations.
+//   rgb_fwd       : RenderingNetwork.forward, 'nerf' and 'idr' mode (mlp.py:208-229), saves the post-ReLU activations.
 #include "ksplit.h"
 #include "mlp_args.h"
 
@@ -239,9 +239,10 @@ __global__ __launch_bounds__(256) void sdf_train_fwd_split_kernel(SdfTrainFwdArg
 
 namespace {
 
-template <int H, int F, int LFV>
+// IDR: the side row in front of the features is [x | PE(view) | normal] (33 of 40 columns) instead of PE(view) (27 of 32)
+template <int H, int F, int LFV, bool IDR = false>
 __global__ __launch_bounds__(256) void rgb_fwd_kernel(RgbFwdArgs a) {
-  constexpr int NT = H / 32, KC = H / 8, PECV = PE<LFV>::PEC, FC = F / 8;
+  constexpr int NT = H / 32, KC = H / 8, PECV = IDR ? cdiv(PE<LFV>::DIM + 6, 8) : PE<LFV>::PEC, FC = F / 8;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hi = lane >> 5;
   const int64_t m = ((int64_t)(blockIdx.x + a.wg0) * 4 + wave) * 32 + (lane & 31);
@@ -251,7 +252,20 @@ __global__ __launch_bounds__(256) void rgb_fwd_kernel(RgbFwdArgs a) {
   float in0[(PECV + FC) * 4];
   {
     float full[PECV * 8], pv[PECV * 4];
-    pe_full<LFV>(a.dirs[ray * 3 + 0], a.dirs[ray * 3 + 1], a.dirs[ray * 3 + 2], full);
+    if constexpr (IDR) {
+      constexpr int PD = PE<LFV>::DIM;
+      float pe[PE<LFV>::PEC * 8];
+      pe_full<LFV>(a.dirs[ray * 3 + 0], a.dirs[ray * 3 + 1], a.dirs[ray * 3 + 2], pe);
+#pragma unroll
+      for (int i = 0; i < PECV * 8; ++i) full[i] = 0.f;
+#pragma unroll
+      for (int i = 0; i < PD; ++i) full[3 + i] = pe[i];
+      fetch_point(a.pts, mc, full[0], full[1], full[2]);
+#pragma unroll
+      for (int j = 0; j < 3; ++j) full[3 + PD + j] = a.normals[mc * 3 + j];
+    } else {
+      pe_full<LFV>(a.dirs[ray * 3 + 0], a.dirs[ray * 3 + 1], a.dirs[ray * 3 + 2], full);
+    }
     to_b_layout<PECV>(full, pv, hi);
     if (a.pev_save) store_regs<PECV>(a.pev_save + m * (PECV * 8), hi, valid, pv);
     float ft[FC * 4];
@@ -414,7 +428,7 @@ extern "C" int i2sdf_rgb_forward(const i2sdf_plan* p, const float* packed, const
   if (!p || !packed || !dirs || !feat || !rgb || M < 0 || n_per_ray <= 0) return I2SDF_EINVAL;
   if (Mp < M || Mp % PTS_PER_WG) return I2SDF_EINVAL;
   const i2sdf_mlp_desc& d = p->rgb.d;
-  if (d.multires != 4) return I2SDF_EINVAL;
+  if (d.multires != 4 || rgb_idr(d)) return I2SDF_EINVAL;          // ('idr' plans: i2sdf_rgb_forward_idr)
   const bool wide = d.hidden == 256 && p->F == 256, x3 = wide && p->rgb_bf16x3;
   if (!wide && !(d.hidden == 64 && p->F == 64)) return I2SDF_EINVAL;
   const Span fwd = span(p, packed, p->rgb, SPAN_FWD);
@@ -445,6 +459,44 @@ extern "C" int i2sdf_rgb_forward(const i2sdf_plan* p, const float* packed, const
   if (wide) i2sdf_dispatch_points(p, st, M, ranged, true, TAIL_BEHIND, full, tail);
   else launch_lds(rgb_fwd_kernel<64, 64, 4>, (unsigned)((M + PTS_PER_WG - 1) / PTS_PER_WG), st, a);
   return i2sdf_hip_check(hipGetLastError(), "rgb_forward launch");
+}
+
+// 'idr' mode (include/i2sdf.h): the same launches over the kernels' IDR instantiations.  No split-K tail: every point goes through full
+// workgroups (rgb_blocked_points covers the whole batch whenever the bf16x3 kernels run, as it does under point ranges).
+extern "C" int i2sdf_rgb_forward_idr(const i2sdf_plan* p, const float* packed, const float* points, const float* cam, const float* dirs,
+                                     const float* z, int64_t ldz, int32_t n_per_ray, const float* normals, const float* feat, int64_t M,
+                                     int64_t Mp, float* rgb, float* rs, float* pev_save, void* stream) {
+  if (M == 0) return I2SDF_OK;                 // empty batch: nothing to validate, nothing to launch
+  if (!p || !packed || !dirs || !normals || !feat || !rgb || M < 0 || n_per_ray <= 0) return I2SDF_EINVAL;
+  if (!points && (!cam || !z || ldz < n_per_ray)) return I2SDF_EINVAL;
+  if (Mp < M || Mp % PTS_PER_WG) return I2SDF_EINVAL;
+  const i2sdf_mlp_desc& d = p->rgb.d;
+  if ((d.multires != 4 && d.multires != 0) || !rgb_idr(d)) return I2SDF_EINVAL;
+  const bool enc = d.multires == 4;               // view directions through PE4, or as they are (embed_type: null)
+  const bool wide = d.hidden == 256 && p->F == 256, x3 = wide && p->rgb_bf16x3;
+  if (!wide && !(d.hidden == 64 && p->F == 64)) return I2SDF_EINVAL;
+  const Span fwd = span(p, packed, p->rgb, x3 ? SPAN_FWD3H : SPAN_FWD);
+  if (!fwd.n_stages) return I2SDF_EINVAL;
+  RgbFwdArgs a{};
+  a.fwd = fwd.w; a.n_fwd = fwd.n_stages;
+  a.L = d.n_lin; a.dirs = dirs; a.n_per_ray = n_per_ray; a.feat = feat; a.M = M; a.Mp = Mp; a.rgb = rgb; a.rs = rs; a.pev_save = pev_save;
+  a.pts = PointSpec{points, cam, dirs, z, ldz, points ? 0 : M, n_per_ray};
+  a.normals = normals;
+  if (x3) a.kcs = rgb_blocked_points(p, M, Mp) > 0 ? KCS_BLK : KCS_PM;
+  hipStream_t st = (hipStream_t)stream;
+  const bool ranged = x3 && i2sdf_parts_on(p);
+  ChainGuard guard(p, st, ranged);
+  auto full = [&](hipStream_t s, int wg0, unsigned g, int64_t Mv) {
+    RgbFwdArgs x = a;
+    x.wg0 = wg0; x.M = Mv;
+    if (x3) i2sdf_launch_rgb_fwd3h_idr(x, enc ? 4 : 0, g, s);
+    else if (wide && enc) launch_lds(rgb_fwd_kernel<256, 256, 4, true>, g, s, x);
+    else if (wide) launch_lds(rgb_fwd_kernel<256, 256, 0, true>, g, s, x);
+    else if (enc) launch_lds(rgb_fwd_kernel<64, 64, 4, true>, g, s, x);
+    else launch_lds(rgb_fwd_kernel<64, 64, 0, true>, g, s, x);
+  };
+  i2sdf_dispatch_points(p, st, M, ranged, false, TAIL_BEHIND, full, [](hipStream_t, int64_t) {});
+  return i2sdf_hip_check(hipGetLastError(), "rgb_forward_idr launch");
 }
 
 // =============================================================================================================

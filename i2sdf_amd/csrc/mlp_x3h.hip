@@ -126,10 +126,28 @@ __global__ __launch_bounds__(NW * 64, 2) void sdf_train_fwd3h_kernel(SdfTrainFwd
   }
 }
 
-// radiance net (RenderingNetwork, 'nerf' mode: mlp.py:208-229) forward and backward
-template <int H, int F, int LFV, int NW>
+// this lane's B-operand values of the 'idr' side row [x | PE(view) | normal], zero padded to whole 32-chunks
+template <int LF>
+__device__ __forceinline__ void side_select_h(const float (&x)[3], float vx, float vy, float vz, const float (&n)[3],
+                                              float (&sel)[cdiv(PE<LF>::DIM + 6, 32) * 8], int kg) {
+  constexpr int PED = PE<LF>::DIM, S32 = cdiv(PED + 6, 32);
+  float full[PE<LF>::PEC * 8], pad[S32 * 32];
+  pe_full<LF>(vx, vy, vz, full);
+#pragma unroll
+  for (int i = 0; i < S32 * 32; ++i) pad[i] = 0.f;
+#pragma unroll
+  for (int i = 0; i < PED; ++i) pad[3 + i] = full[i];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) { pad[j] = x[j]; pad[3 + PED + j] = n[j]; }
+  x3h_select<S32>(pad, sel, kg);
+}
+
+// radiance net (RenderingNetwork, mlp.py:208-229) forward and backward.  IDR: the side row in front of the features is [x | PE(view) | normal]
+// (two 32-chunks, saved 40 wide) instead of PE(view) (one 32-chunk, saved 32 wide); backward: two more tiles in the last reverse product, the
+// three normal rows of W_0^T in the first of them (plan.cpp: build_rgb) -> nbar
+template <int H, int F, int LFV, int NW, bool IDR = false>
 __global__ __launch_bounds__(NW * 64, 2) void rgb_fwd3h_kernel(RgbFwdArgs a) {
-  constexpr int NT = H / 16, KH32 = H / 32, PECV = PE<LFV>::PEC, PV32 = cdiv(PE<LFV>::DIM, 32);
+  constexpr int NT = H / 16, KH32 = H / 32, PECV = IDR ? cdiv(PE<LFV>::DIM + 6, 8) : PE<LFV>::PEC, PV32 = cdiv(PE<LFV>::DIM + (IDR ? 6 : 0), 32);
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, kg = lane >> 4;
   const int64_t m = ((int64_t)(blockIdx.x + a.wg0) * NW + wave) * HP + (lane & 15);
@@ -137,7 +155,15 @@ __global__ __launch_bounds__(NW * 64, 2) void rgb_fwd3h_kernel(RgbFwdArgs a) {
   const int64_t mc = valid ? m : a.M - 1;
   const int64_t ray = mc / a.n_per_ray;
   float pev[PV32 * 8];
-  pe_select_h<LFV>(a.dirs[ray * 3 + 0], a.dirs[ray * 3 + 1], a.dirs[ray * 3 + 2], pev, kg);
+  if constexpr (IDR) {
+    float x[3], n[3];
+    fetch_point(a.pts, mc, x[0], x[1], x[2]);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) n[j] = a.normals[mc * 3 + j];
+    side_select_h<LFV>(x, a.dirs[ray * 3 + 0], a.dirs[ray * 3 + 1], a.dirs[ray * 3 + 2], n, pev, kg);
+  } else {
+    pe_select_h<LFV>(a.dirs[ray * 3 + 0], a.dirs[ray * 3 + 1], a.dirs[ray * 3 + 2], pev, kg);
+  }
   if (a.pev_save) store_pe_row_h<PECV>(a.pev_save + m * (PECV * 8), kg, valid, pev);
   const int64_t lstride = a.Mp * H;
   const int kcs = a.kcs;
@@ -196,7 +222,7 @@ __global__ __launch_bounds__(NW * 64, 2) void light_fwd3h_kernel(LightFwd3hArgs 
   if (valid && kg == 0) a.lm[m] = 1.0f / (1.0f + expf(-o[0]));
 }
 
-template <int H, int F, int NW>
+template <int H, int F, int NW, bool IDR = false>
 __global__ __launch_bounds__(NW * 64, 2) void rgb_bwd3h_kernel(RgbBwdArgs a) {
   constexpr int NT = H / 16, KH32 = H / 32, FT = F / 16;
   static_assert(FT == NT, "feature tiles reuse the hidden accumulator set");
@@ -268,7 +294,22 @@ __global__ __launch_bounds__(NW * 64, 2) void rgb_bwd3h_kernel(RgbBwdArgs a) {
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) accA[nt] = accB[nt];
   }
-  {
+  if constexpr (IDR) {
+    XhMaskSrc<NT> src{accA, a.rs + mcrow, a.gar + mrow, kg, valid, kcs};     // G(a_0), then the feature rows and the normal rows of W_0^T
+    f32x4 accN[FT + 2];
+#pragma unroll
+    for (int nt = 0; nt < FT + 2; ++nt) accN[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    dense_x3h<FT + 2, KH32, 0, NW>(ws, src, accN, tid);
+    if (valid) {
+#pragma unroll
+      for (int nt = 0; nt < FT; ++nt) stg4(a.fbar + mc * F + 16 * nt + 4 * kg, accN[nt]);
+      if (kg == 0) {                 // tile FT, registers 0..2 of the lanes with kg == 0: rows 0..2 = the normal columns
+        float* nrow = a.nbar + m * 3;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) nrow[j] = a.nbar_acc ? nrow[j] + accN[FT][j] : accN[FT][j];
+      }
+    }
+  } else {
     XhMaskSrc<NT> src{accA, a.rs + mcrow, a.gar + mrow, kg, valid, kcs};     // G(a_0), then the feature rows of W_0^T
     zero(accB);
     dense_x3h<FT, KH32, 0, NW>(ws, src, accB, tid);
@@ -289,3 +330,8 @@ void i2sdf_launch_train_fwd3h(const SdfTrainFwdArgs& a, unsigned grid, hipStream
 void i2sdf_launch_rgb_fwd3h(const RgbFwdArgs& a, unsigned grid, hipStream_t st) { launch_lds_threads(512, rgb_fwd3h_kernel<256, 256, 4, 8>, grid, st, a); }
 void i2sdf_launch_light_fwd3h(const LightFwd3hArgs& a, unsigned grid, hipStream_t st) { launch_lds_threads(8 * 64, light_fwd3h_kernel<128, 256, 8>, grid, st, a); }
 void i2sdf_launch_rgb_bwd3h(const RgbBwdArgs& a, unsigned grid, hipStream_t st) { launch_lds_threads(512, rgb_bwd3h_kernel<256, 256, 8>, grid, st, a); }
+void i2sdf_launch_rgb_fwd3h_idr(const RgbFwdArgs& a, int view_multires, unsigned grid, hipStream_t st) {
+  if (view_multires == 4) launch_lds_threads(512, rgb_fwd3h_kernel<256, 256, 4, 8, true>, grid, st, a);
+  else launch_lds_threads(512, rgb_fwd3h_kernel<256, 256, 0, 8, true>, grid, st, a);
+}
+void i2sdf_launch_rgb_bwd3h_idr(const RgbBwdArgs& a, unsigned grid, hipStream_t st) { launch_lds_threads(512, rgb_bwd3h_kernel<256, 256, 8, true>, grid, st, a); }

@@ -57,7 +57,7 @@ Seg base_seg(const NetPlan& np, int l, int type) {
   return s;
 }
 
-int pe_dim(const i2sdf_mlp_desc& d) { return d.multires > 0 ? d.d_in + 2 * d.d_in * d.multires : d.d_in; }
+int pe_dim(const i2sdf_mlp_desc& d) { return side_dim(d); }      // (plan.h: one definition for every caller)
 int pe_chunks(const i2sdf_mlp_desc& d) { return cdiv(pe_dim(d), 8); }
 
 ColMap cols(int n) { return ColMap{HUGE_SPLIT, 0, n, 0, 0}; }      // the first n columns, no split
@@ -221,13 +221,17 @@ int build_sdf(i2sdf_plan* p, Builder& b) {
   return I2SDF_OK;
 }
 
-// ---- radiance net ('nerf' mode): input [PE(view) | feature] ---------------------------------------
+// ---- radiance net: input [side row | feature]; side row = PE(view) ('nerf') or [x | PE(view) | normal] ('idr'; plan.h: side_dim) ----
 int build_rgb(i2sdf_plan* p, Builder& b) {
   NetPlan& np = p->rgb;
   const i2sdf_mlp_desc& d = np.d;
-  const int L = d.n_lin, H = d.hidden, PEC = pe_chunks(d), PED = pe_dim(d), F = p->F;
+  const bool idr = rgb_idr(d);
+  const int L = d.n_lin, H = d.hidden, PED = pe_dim(d), PEC = cdiv(PED, 8), F = p->F;
   if (check_mlp(d)) return I2SDF_EINVAL;
-  if (d.skip_layer >= 0 || d.d_out != 3 || d.multires <= 0 || d.in0 != PED + F || F <= 0) return I2SDF_EINVAL;
+  if ((d.reserved != I2SDF_RGB_MODE_NERF && !idr) || (idr && d.d_in != 9)) return I2SDF_EINVAL;
+  // the reverse product of layer 0: the feature rows of W_0^T; 'idr' adds one more tile behind them that holds the three normal rows
+  const ColMap rev0 = idr ? ColMap{F, PED, F, PED - 3, 3} : ColMap{HUGE_SPLIT, PED, F, 0, 0};
+  if (d.skip_layer >= 0 || d.d_out != 3 || (d.multires <= 0 && !idr) || d.in0 != PED + F || F <= 0) return I2SDF_EINVAL;
   for (int l = 0; l < L - 1; ++l)
     if (d.out_dim[l] != H || d.in_dim[l] != (l == 0 ? PED + F : H)) return I2SDF_EINVAL;
   const bool wide = H == 256 && F == 256 && L >= 3;      // (the radiance net's bf16x3 kernels all run on 16-point waves)
@@ -238,7 +242,7 @@ int build_rgb(i2sdf_plan* p, Builder& b) {
   mark_here(np, b, {FWD_END, REV});
   emit_rowvec(b, np, L - 1, FP32, 3);
   for (int l = L - 2; l >= 1; --l) emit_dense_bwd(b, np, l, SEG_WBWD, H / 32, H / 8, cols(H), 0, H);
-  emit_dense_bwd(b, np, 0, SEG_WBWD, F / 32, H / 8, ColMap{HUGE_SPLIT, PED, F, 0, 0}, 0, H);   // feature columns only
+  emit_dense_bwd(b, np, 0, SEG_WBWD, F / 32 + (idr ? 1 : 0), H / 8, rev0, 0, H);   // feature columns only ('idr': + the normal columns)
   mark_here(np, b, {REV_END});
   // bf16x3 streams, 16-point-wave family (x3h.h): layer 0 reduces over [PE(view) padded to 32-chunks | feature]
   mark_here(np, b, {FWD3H, FWD3H_END, REV3H, REV3H_END});
@@ -250,7 +254,7 @@ int build_rgb(i2sdf_plan* p, Builder& b) {
     mark_here(np, b, {FWD3H_END, REV3H});
     emit_rowvec(b, np, L - 1, X3H, 3);
     for (int l = L - 2; l >= 1; --l) emit_dense_bwd(b, np, l, SEG_WBWD3H, H / 16, H / 32, cols(H), 0, H);
-    emit_dense_bwd(b, np, 0, SEG_WBWD3H, F / 16, H / 32, ColMap{HUGE_SPLIT, PED, F, 0, 0}, 0, H);
+    emit_dense_bwd(b, np, 0, SEG_WBWD3H, F / 16 + (idr ? 2 : 0), H / 32, rev0, 0, H);      // (tiles come in pairs)
     mark_here(np, b, {REV3H_END});
   }
   return I2SDF_OK;
@@ -283,7 +287,7 @@ int build_light(i2sdf_plan* p, Builder& b) {
 // kind: 0 = sdf net, 1 = radiance net, 2 = light head
 void assign_scales_and_wgrad(i2sdf_plan* p, NetPlan& np, int kind) {
   const i2sdf_mlp_desc& d = np.d;
-  const int PEC8 = pe_chunks(d) * 8;
+  const int side = pe_dim(d), PEC8 = cdiv(side, 8) * 8;
   for (int l = 0; l < d.n_lin; ++l) {
     np.scale_off[l] = p->n_scale;
     p->n_scale += d.out_dim[l];
@@ -295,7 +299,7 @@ void assign_scales_and_wgrad(i2sdf_plan* p, NetPlan& np, int kind) {
       else if (l == d.skip_layer) colsP = d.hidden + PEC8;
       if (last) rowsP = 32 + (d.d_out - 1);
     } else if (kind == 1) {
-      if (l == 0) colsP = PEC8 + (d.in0 - pe_dim(d));
+      if (l == 0) colsP = PEC8 + (d.in0 - side);
       if (last) rowsP = 32;
     } else {
       if (l == 0) colsP = d.in0;
@@ -312,12 +316,16 @@ void assign_scales_and_wgrad(i2sdf_plan* p, NetPlan& np, int kind) {
 extern "C" int i2sdf_plan_create(const i2sdf_net_desc* desc, i2sdf_plan** out) {
   if (!desc || !out) return I2SDF_EINVAL;
   {  // shapes the kernels are instantiated for: refuse anything else here, with the reason (i2sdf_last_hip_error), not at the first launch
-    const int H = desc->sdf.hidden, Hr = desc->rgb.hidden, F = desc->rgb.n_lin > 0 ? desc->rgb.in0 - (desc->rgb.multires > 0 ? 3 + 6 * desc->rgb.multires : 3) : 0;
+    const int H = desc->sdf.hidden, Hr = desc->rgb.hidden, F = desc->rgb.n_lin > 0 ? desc->rgb.in0 - (rgb_idr(desc->rgb) ? side_dim(desc->rgb) : (desc->rgb.multires > 0 ? 3 + 6 * desc->rgb.multires : 3)) : 0;
     const bool ok = (H == 256 && Hr == 256 && F == 256) || (H == 64 && Hr == 64 && F == 64);
     if (!ok || desc->sdf.multires != 6 || (desc->rgb.multires != 4 && desc->rgb.multires != 0)) {
       g_hip_err = "i2sdf_plan_create: SDF width " + std::to_string(H) + " / radiance width " + std::to_string(Hr) + " / feature size " + std::to_string(F) +
                   " / multires " + std::to_string(desc->sdf.multires) + "," + std::to_string(desc->rgb.multires) +
                   ": the MLP kernels are instantiated for 256/256/256 and 64/64/64 with multires 6 (points) and 4 (view directions) only";
+      return I2SDF_EINVAL;
+    }
+    if (rgb_idr(desc->rgb) && desc->rgb.d_in != 9) {
+      g_hip_err = "i2sdf_plan_create: the radiance net's 'idr' mode needs d_in 9 (points, view directions, normals)";
       return I2SDF_EINVAL;
     }
   }

@@ -67,6 +67,16 @@ constexpr SpanId SPAN_FWD3H{FWD3H, FWD3H_END, SCH};
 constexpr SpanId SPAN_REV3H{REV3H, REV3H_END, SCH};
 constexpr SpanId SPAN_FWD2H{FWD2H, FWD2H_END, SCH};
 
+// Radiance net: the columns of layer 0 in front of the feature columns are the per-point "side row" -- 'nerf': PE(view); 'idr':
+// [x | PE(view) | normal] (include/i2sdf.h: I2SDF_RGB_MODE_*), one contiguous block of lin0.weight_v in either mode
+// side_dim: THE width of a net's encoded input in front of the hidden / feature columns of its layer 0 -- PE(x) of the SDF net, the side row
+// of the radiance net, d_in of a net without encoding (plan.cpp, wgrad.hip and the launch sites all take it from here)
+inline bool rgb_idr(const i2sdf_mlp_desc& d) { return d.reserved == I2SDF_RGB_MODE_IDR; }
+inline int side_dim(const i2sdf_mlp_desc& d) {
+  const int raw = rgb_idr(d) ? 3 : d.d_in;          // 'idr': only the view direction (3 of the 9 raw inputs) is encoded
+  return (d.multires > 0 ? raw + 2 * raw * d.multires : raw) + (rgb_idr(d) ? 6 : 0);
+}
+
 struct NetPlan {
   i2sdf_mlp_desc d;
   int32_t scale_off[I2SDF_MAX_LAYERS];

@@ -75,7 +75,8 @@ extern "C" int i2sdf_render_image(const i2sdf_plan* p, const float* packed, cons
     }
     rc = i2sdf_sdf_forward_grad(p, packed, nullptr, q.cam, q.dirs, q.z, n_z, n, M, M, Mp, q.sdf, q.feat, q.grad, q.hs, nullptr, nullptr, stream);
     if (rc) return rc;
-    rc = i2sdf_rgb_forward(p, packed, q.dirs, n, q.feat, M, Mp, q.rgb, nullptr, nullptr, stream);
+    if (i2sdf::rgb_idr(p->rgb.d)) rc = i2sdf_rgb_forward_idr(p, packed, nullptr, q.cam, q.dirs, q.z, n_z, n, q.grad, q.feat, M, Mp, q.rgb, nullptr, nullptr, stream);
+    else rc = i2sdf_rgb_forward(p, packed, q.dirs, n, q.feat, M, Mp, q.rgb, nullptr, nullptr, stream);
     if (rc) return rc;
     if (light) {
       rc = i2sdf_light_forward(p, packed, q.feat, M, Mp, q.lm, nullptr, stream);

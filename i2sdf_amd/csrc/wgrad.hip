@@ -1070,8 +1070,8 @@ struct TaskList {
 
 void fill_wn(WnTab& tab, const NetPlan& np, int kind, int& row0) {
   const i2sdf_mlp_desc& d = np.d;
-  const int PEC8 = (d.multires > 0 ? cdiv(d.d_in + 2 * d.d_in * d.multires, 8) : 0) * 8;
-  const int PED = d.multires > 0 ? d.d_in + 2 * d.d_in * d.multires : d.d_in;
+  const bool enc = d.multires > 0 || rgb_idr(d);        // a PE / side block in front of the hidden or feature columns (plan.h: side_dim)
+  const int PED = side_dim(d), PEC8 = enc ? cdiv(PED, 8) * 8 : 0;
   for (int l = 0; l < d.n_lin; ++l) {
     WnLayer& y = tab.l[tab.n++];
     y.off_v = d.off_v[l]; y.off_g = d.off_g[l]; y.off_bias = d.off_bias[l];

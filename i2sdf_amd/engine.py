@@ -95,7 +95,8 @@ class RenderEngine:
         self._timed_lib = type("TimedLib", (), {})()
         for name in L.SIGNATURES:
             fn = getattr(self._lib, name)
-            if name in ("i2sdf_sdf_forward", "i2sdf_sdf_forward_grad", "i2sdf_rgb_forward", "i2sdf_rgb_backward", "i2sdf_sdf_backward",
+            if name in ("i2sdf_sdf_forward", "i2sdf_sdf_forward_grad", "i2sdf_rgb_forward", "i2sdf_rgb_backward", "i2sdf_rgb_forward_idr", "i2sdf_rgb_backward_idr",
+                        "i2sdf_sdf_backward",
                         "i2sdf_weight_grads", "i2sdf_sample_rays", "i2sdf_composite_forward", "i2sdf_composite_backward", "i2sdf_pack_weights",
                         "i2sdf_ray_setup", "i2sdf_light_forward", "i2sdf_light_backward"):
                 fn = _Timed(fn, name)
@@ -371,22 +372,62 @@ class RenderEngine:
                  "i2sdf_sdf_forward_grad")
         return out
 
-    def rgb_forward(self, dirs, n_per_ray, feat, M, save=True):
+    @property
+    def idr(self) -> bool:
+        """rendering_network.mode == 'idr': the radiance net also takes the points and the normals (include/i2sdf.h: I2SDF_RGB_MODE_IDR)"""
+        return self.cfg.rgb_mode == "idr"
+
+    def rgb_forward(self, dirs, n_per_ray, feat, M, save=True, fw=None, points=None, normals=None):
+        """'idr' mode needs the points and normals of the M points: `fw`, the dict of the sdf_forward_grad call that produced `feat` (its
+        leading M points are ray samples), or explicit `points` (M,3) and `normals` (M,3).  `pev` is the saved side row: (Mp,32) PE(view)
+        in 'nerf' mode, (Mp,40) [x | PE(view) | normal] in 'idr' mode ((Mp,16) with unencoded view directions)."""
         Mp = feat.shape[0]
         rgb = torch.empty(M, 3, dtype=torch.float32, device=feat.device)
         Lr, Hr = self.cfg.rgb.n_lin, self.cfg.rgb.hidden
         rs = self._ws(Lr - 1, Mp, Hr, device=feat.device) if save else None
-        pev = self._ws(Mp, 32, device=feat.device) if save else None
+        pev = self._ws(Mp, (self.cfg.rgb.pe_dim + 7) // 8 * 8 if self.idr else 32, device=feat.device) if save else None
+        if self.idr:
+            cam = z = pts = None
+            ldz = 0
+            if points is not None:
+                pts = points.detach().to(torch.float32).contiguous()
+                if pts.shape[0] < M:
+                    raise ValueError(f"rgb_forward: {pts.shape[0]} points for {M} radiance samples")
+            else:
+                if fw is None or fw["rays"][2] is None or fw["n_ray_pts"] < M or fw["rays"][3] != n_per_ray:
+                    raise ValueError("rgb_forward ('idr' mode): needs the sdf_forward_grad result whose leading ray samples are the M points, or `points`")
+                cam, _, z, _ = fw["rays"]
+                ldz = z.shape[1]
+            nrm = normals if normals is not None else (fw["grad"] if fw is not None else None)
+            if nrm is None or nrm.shape[0] < M:
+                raise ValueError("rgb_forward ('idr' mode): needs the normals (d sdf/dx) of the M points")
+            nrm = nrm.detach().to(torch.float32).contiguous()
+            dirs = dirs.contiguous()
+            if dirs.shape[0] * n_per_ray < M:
+                raise ValueError(f"rgb_forward: {dirs.shape[0]} view directions x {n_per_ray} samples for {M} points")
+            L.check(self._lib.i2sdf_rgb_forward_idr(self._plan, self._pk(), L.ptr(pts), L.ptr(cam), L.ptr(dirs), L.ptr(z), ldz, n_per_ray,
+                                                    L.ptr(nrm), L.ptr(feat), M, Mp, L.ptr(rgb), L.ptr(rs), L.ptr(pev), L.stream_ptr()),
+                    "i2sdf_rgb_forward_idr")
+            return rgb, rs, pev
         L.check(self._lib.i2sdf_rgb_forward(self._plan, self._pk(), L.ptr(dirs.contiguous()), n_per_ray, L.ptr(feat), M, Mp,
                                              L.ptr(rgb), L.ptr(rs), L.ptr(pev), L.stream_ptr()), "i2sdf_rgb_forward")
         return rgb, rs, pev
 
-    def rgb_backward(self, rgb, rgb_bar, rs, M):
+    def rgb_backward(self, rgb, rgb_bar, rs, M, nbar=None, accumulate=True):
+        """'idr' mode: `nbar` (>= M, 3) takes d loss / d normal through the radiance net -- added to its rows [0, M) (accumulate: the
+        `nbar` that sdf_backward gets, after the compositing backward wrote it) or written to them."""
         Mp, dev = rs.shape[1], rs.device
         Lr, Hr = self.cfg.rgb.n_lin, self.cfg.rgb.hidden
         gar = self._ws(Lr - 1, Mp, Hr, device=dev)
         ga_last = self._ws(Mp, 4, device=dev)
         fbar = self._ws(Mp, self.F, device=dev)
+        if self.idr:
+            if nbar is None or nbar.shape[0] < M or nbar.dtype != torch.float32 or not nbar.is_contiguous():
+                raise ValueError("rgb_backward ('idr' mode): needs a contiguous fp32 `nbar` of at least M rows")
+            L.check(self._lib.i2sdf_rgb_backward_idr(self._plan, self._pk(), L.ptr(rgb), L.ptr(rgb_bar.contiguous()), L.ptr(rs), M, Mp,
+                                                     L.ptr(gar), L.ptr(ga_last), L.ptr(fbar), L.ptr(nbar), int(bool(accumulate)), L.stream_ptr()),
+                    "i2sdf_rgb_backward_idr")
+            return gar, ga_last, fbar
         L.check(self._lib.i2sdf_rgb_backward(self._plan, self._pk(), L.ptr(rgb), L.ptr(rgb_bar.contiguous()), L.ptr(rs), M, Mp,
                                               L.ptr(gar), L.ptr(ga_last), L.ptr(fbar), L.stream_ptr()), "i2sdf_rgb_backward")
         return gar, ga_last, fbar

@@ -76,6 +76,7 @@ OPT_SAMPLER_BF16X2 = 1024
 OPT_SAVES24 = 2048
 MAX_PARTS = 4
 GRID_ORDER_MESHGRID, GRID_ORDER_VOLUME = 0, 1
+RGB_MODE_NERF, RGB_MODE_IDR = 0, 1    # I2SDF_RGB_MODE_*: i2sdf_net_desc.rgb.reserved
 RASTER_SMALL_MAX = 64            # I2SDF_RASTER_SMALL_MAX
 TSDF_MAX_CELLS = 1 << 24         # I2SDF_TSDF_MAX_CELLS
 IMAGE_STATS = 8                  # I2SDF_IMAGE_STATS
@@ -113,6 +114,10 @@ SIGNATURES = {
     "i2sdf_rgb_forward": (C.c_int, [_P, _P, _P, _I32, _P, _I64, _I64, _P, _P, _P, _P]),
     # plan, packed, rgb, rgb_bar, rs, M, Mp, gar, ga_last, fbar, stream
     "i2sdf_rgb_backward": (C.c_int, [_P] * 5 + [_I64, _I64] + [_P] * 4),
+    # plan, packed, points, cam, dirs, z, ldz, n_per_ray, normals, feat, M, Mp, rgb, rs, pev_save, stream
+    "i2sdf_rgb_forward_idr": (C.c_int, [_P] * 6 + [_I64, _I32, _P, _P, _I64, _I64] + [_P] * 4),
+    # plan, packed, rgb, rgb_bar, rs, M, Mp, gar, ga_last, fbar, nbar, accumulate, stream
+    "i2sdf_rgb_backward_idr": (C.c_int, [_P] * 5 + [_I64, _I64] + [_P] * 4 + [_I32, _P]),
     # plan, packed, points, cam, dirs, z, ldz, n_per_ray, n_ray_pts, M, Mp, hs, abars, sbar, fbar, m_fbar, nbar, gus, gpbar, gas,
     # ga_last4, ones4, stream
     "i2sdf_sdf_backward": (C.c_int, [_P] * 6 + [_I64, _I32, _I64, _I64, _I64] + [_P] * 4 + [_I64] + [_P] * 7),

@@ -106,7 +106,7 @@ class _RenderFn(torch.autograd.Function):
         # one chain: with point ranges on (engine.parts) every range runs SDF forward -> d sdf/dx -> radiance net on its own stream
         with eng.chain(M_main + n_extra):
             fw = eng.sdf_forward_grad(points=st["extra_pts"], rays=(st["cam"], st["dirs"], st["z_all"], n), want_grad=True, save=True)
-            rgb, rs, pev = eng.rgb_forward(st["dirs"], n, fw["feat"], M_main, save=True)
+            rgb, rs, pev = eng.rgb_forward(st["dirs"], n, fw["feat"], M_main, save=True, fw=fw)      # ('idr': points and normals of fw)
         lm = hl = None
         if net.use_light:
             lm, hl = eng.light_forward(fw["feat"], M_main, save=True)
@@ -197,7 +197,8 @@ class _RenderFn(torch.autograd.Function):
             light = {"hl": ctx.hl, "gal0": gal0, "gal_last": gal_last}
         # one chain: radiance backward -> SDF sweeps -> weight-gradient GEMMs per point range (i2sdf_weight_grads joins the ranges)
         with eng.chain(M_sdf):
-            gar, ga_last, fbar = eng.rgb_backward(ctx.rgb, cb["rgb_bar"], ctx.rs, M_main)
+            # ('idr' mode: d loss / d normal through the radiance net is added to nbar's ray rows here, behind the compositing backward)
+            gar, ga_last, fbar = eng.rgb_backward(ctx.rgb, cb["rgb_bar"], ctx.rs, M_main, nbar=nbar)
             bw = eng.sdf_backward(fw, sbar=sbar, fbar=fbar, m_fbar=M_main, nbar=nbar)
             eng.weight_grads(flat, gflat, fw, bw, M_main=M_main, fbar=fbar, rgb_fw={"pev": ctx.pev, "rs": ctx.rs},
                              rgb_bw={"gar": gar, "ga_last": ga_last}, light=light)
@@ -242,7 +243,7 @@ class _RenderFn(torch.autograd.Function):
             gal0, gal_last = eng.light_backward(ctx.lm, lmask_bar, ctx.hl, M_main)
             light = {"hl": ctx.hl, "gal0": gal0, "gal_last": gal_last}
         with eng.chain(fw["M"]):
-            gar, ga_last, fbar = eng.rgb_backward(ctx.rgb, rgb_bar, ctx.rs, M_main)
+            gar, ga_last, fbar = eng.rgb_backward(ctx.rgb, rgb_bar, ctx.rs, M_main, nbar=nbar)      # ('idr': += into nbar's ray rows)
             bw = eng.sdf_backward(fw, sbar=sbar, fbar=fbar, m_fbar=M_main, nbar=nbar)
             eng.weight_grads(flat, gflat, fw, bw, M_main=M_main, fbar=fbar, rgb_fw={"pev": ctx.pev, "rs": ctx.rs},
                              rgb_bw={"gar": gar, "ga_last": ga_last}, light=light)
@@ -763,9 +764,9 @@ class I2SDFNetwork(nn.Module):
             extra_pts, n_eik, n_pc = (None, 0, 0)
             if with_eik:
                 extra_pts, n_eik, n_pc = self._extra_points(input, cam, dirs, z_eik, draws)
-            returns_grad = self.use_normal or (not training) or with_eik
+            returns_grad = self.use_normal or (not training) or with_eik or eng.idr      # (model/network/__init__.py:109)
             fw = eng.sdf_forward_grad(points=extra_pts, rays=(cam, dirs, z_all.contiguous(), n), want_grad=returns_grad, save=False)
-            rgb, _, _ = eng.rgb_forward(dirs, n, fw["feat"], M_main, save=False)
+            rgb, _, _ = eng.rgb_forward(dirs, n, fw["feat"], M_main, save=False, fw=fw)
             lm = None
             if self.use_light:
                 lm, _ = eng.light_forward(fw["feat"], M_main, save=False)

@@ -50,7 +50,7 @@ typedef struct i2sdf_mlp_desc {
   int32_t d_out;                          /* rows of the last layer                                  */
   int32_t multires;                       /* positional-encoding frequencies L (embedder.py:138-152) */
   int32_t skip_layer;                     /* l with `l in skip_in` (mlp.py:94), -1 if none           */
-  int32_t reserved;
+  int32_t reserved;                       /* radiance net: I2SDF_RGB_MODE_* (0 = 'nerf'); 0 for the other nets */
   int32_t out_dim[I2SDF_MAX_LAYERS];      /* rows of weight_v per layer                              */
   int32_t in_dim[I2SDF_MAX_LAYERS];       /* cols of weight_v per layer                              */
   int64_t off_bias[I2SDF_MAX_LAYERS];
@@ -58,9 +58,18 @@ typedef struct i2sdf_mlp_desc {
   int64_t off_v[I2SDF_MAX_LAYERS];
 } i2sdf_mlp_desc;
 
+/* rendering_network.mode (mlp.py:185-216), carried by i2sdf_net_desc.rgb.reserved.  It decides the columns of lin0.weight_v in front of the
+ * feature columns -- the per-point "side row" of the radiance net:
+ *   I2SDF_RGB_MODE_NERF  [PE4(view_dir) (27)]                          d_in = 3, in0 = 27 + F
+ *   I2SDF_RGB_MODE_IDR   [point (3) | PE4(view_dir) (27) | normal (3)]  d_in = 9, in0 = 33 + F   (normal = the raw d sdf/dx, not normalised)
+ *                        multires 0 (no view encoding): [point | view_dir | normal], in0 = 9 + F
+ * d_in has to agree with the mode; i2sdf_plan_create refuses anything else. */
+#define I2SDF_RGB_MODE_NERF 0
+#define I2SDF_RGB_MODE_IDR 1
+
 typedef struct i2sdf_net_desc {
   i2sdf_mlp_desc sdf;                     /* ImplicitNetwork: PE(x) -> softplus100 stack -> [sdf | feature]   */
-  i2sdf_mlp_desc rgb;                     /* RenderingNetwork 'nerf': [PE(view) | feature] -> ReLU -> sigmoid */
+  i2sdf_mlp_desc rgb;                     /* RenderingNetwork: [side row | feature] -> ReLU -> sigmoid        */
   i2sdf_mlp_desc light;                   /* light-mask head (n_lin == 0 when absent)                         */
   int64_t off_beta;                       /* density.beta                                                     */
   int64_t n_params;                       /* total floats in `params`                                         */
@@ -94,7 +103,7 @@ void i2sdf_plan_destroy(i2sdf_plan* plan);
 #define I2SDF_OPT_TRAIN_FWD_BF16X3 4
 /*   I2SDF_OPT_SDF_BWD_BF16X3: the full workgroups of i2sdf_sdf_backward (both sweeps, 256-wide nets). */
 #define I2SDF_OPT_SDF_BWD_BF16X3 8
-/*   I2SDF_OPT_RGB_BF16X3: the full workgroups of i2sdf_rgb_forward / i2sdf_rgb_backward (256-wide nets), and i2sdf_light_forward of the
+/*   I2SDF_OPT_RGB_BF16X3: the full workgroups of i2sdf_rgb_forward / i2sdf_rgb_backward and their _idr twins (256-wide nets), and i2sdf_light_forward of the
  *   128-unit light-mask head on 256 features. */
 #define I2SDF_OPT_RGB_BF16X3 16
 /*   I2SDF_OPT_TAIL_OVERLAP: the split-K tail workgroups of i2sdf_sdf_forward_grad and i2sdf_sdf_backward (the partial last
@@ -118,7 +127,7 @@ void i2sdf_plan_destroy(i2sdf_plan* plan);
  *   bf16x3 form.  Default 0; every other kernel keeps the fp32-equivalent bf16x3 / fp32 arithmetic. */
 #define I2SDF_OPT_WGRAD_BF16X2 256
 /*   I2SDF_OPT_PARTS (value n = 2..I2SDF_MAX_PARTS, 0 / 1 = off; 256-wide nets with the bf16x3 options on): the per-point entry points
- *   (i2sdf_sdf_forward_grad, i2sdf_rgb_forward, i2sdf_rgb_backward, i2sdf_sdf_backward, the GEMMs of i2sdf_weight_grads) cut their
+ *   (i2sdf_sdf_forward_grad, i2sdf_rgb_forward, i2sdf_rgb_backward and their _idr twins, i2sdf_sdf_backward, the GEMMs of i2sdf_weight_grads) cut their
  *   point batch into n ranges at multiples of i2sdf_wgrad_chunk_points(); range 0 runs on the caller's stream, the others on streams
  *   owned by the plan.  On its own an entry point forks and joins (it returns stream-ordered on the caller's stream, as without the
  *   option).  Between i2sdf_chain_begin and i2sdf_chain_end the ranges stay un-joined ACROSS entry points: every range runs its own
@@ -144,7 +153,7 @@ void i2sdf_plan_destroy(i2sdf_plan* plan);
 #define I2SDF_OPT_SAVES24 2048
 /* number of leading points (a multiple of 32) of a batch whose saved tensors are blocked under the current options: which = 0
  * hs / abars / gus / gas of an i2sdf_sdf_forward_grad batch of M points (has_feat: feat != NULL in that call), which = 1 rs / gar
- * of an i2sdf_rgb_forward batch.  Element (point m < that count, column c) of a blocked (Mp,256) tensor lives at float offset
+ * of an i2sdf_rgb_forward batch (of an i2sdf_rgb_forward_idr batch: Mp or 0, that mode has no split-K tail).  Element (point m < that count, column c) of a blocked (Mp,256) tensor lives at float offset
  * (m/32)*8192 + (c/16)*512 + (m%32)*16 + c%16; points behind the count are ordinary rows m*256 + c.
  * which = 2: the leading points whose abars / gus / gas are packed 24-bit records under the current options (I2SDF_OPT_SAVES24: Mp -- every point --
  * or 0).  A packed layer holds, per 32-point block (6144 floats, dense) and 16-column k-chunk (384 floats): 32 x 2 x 4 dwords of upper halves
@@ -219,12 +228,40 @@ int i2sdf_rgb_forward(const i2sdf_plan* plan, const float* packed, const float* 
                       int64_t M, int64_t Mp, float* rgb, float* rs, float* pev_save, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Radiance network forward, 'idr' mode (mlp.py:208-216; a plan whose rgb.reserved is I2SDF_RGB_MODE_IDR -- i2sdf_rgb_forward returns
+ * I2SDF_EINVAL on such a plan, this entry point on a 'nerf' plan): rgb = sigmoid(MLP([x | PE4(view_dir) | normal | feature])).
+ * The 33-wide side row [x | PE(view) | normal] is assembled per point in registers:
+ *   x       points (M,3) when given, else cam[r] + z[r*ldz + j] * dirs[r] with r = m / n_per_ray, j = m % n_per_ray (as i2sdf_sdf_forward_grad)
+ *   view    dirs[m / n_per_ray], as in 'nerf' mode
+ *   normal  normals (M,3): the `grad` output of i2sdf_sdf_forward_grad, used as it is
+ *   rgb (M,3) ; rs (L-1, Mp, H) post-ReLU activations and pev_save (Mp,40) the side row, zero padded (NULL if no backward follows)
+ *   With the view directions unencoded (rgb.multires 0: embed_type null) the side row is [x | view_dir | normal], 9 wide, pev_save (Mp,16).
+ * d loss / d x is not formed by the backward: the points carry no parameter dependence (the sampler runs without grad).
+ * Honours I2SDF_OPT_RGB_BF16X3, I2SDF_OPT_PARTS and I2SDF_OPT_BLOCKED_SAVES as i2sdf_rgb_forward does; every point goes through full
+ * 128-point workgroups (no split-K tail in this mode, so the blocked prefix of rs is the whole batch).
+ * ---------------------------------------------------------------------------------------------- */
+int i2sdf_rgb_forward_idr(const i2sdf_plan* plan, const float* packed, const float* points, const float* cam, const float* dirs,
+                          const float* z, int64_t ldz, int32_t n_per_ray, const float* normals, const float* feat, int64_t M, int64_t Mp,
+                          float* rgb, float* rs, float* pev_save, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Backward of the radiance network (autograd through mlp.py:208-229).
  *   rgb (M,3) forward output, rgb_bar (M,3) upstream, rs from the forward
  *   -> gar (L-1, Mp, H) G(a_l) l=0..L-2 ; ga_last (Mp,4) G(a_{L-1}) ; fbar (Mp,F) d loss / d feature
  * ---------------------------------------------------------------------------------------------- */
 int i2sdf_rgb_backward(const i2sdf_plan* plan, const float* packed, const float* rgb, const float* rgb_bar, const float* rs,
                        int64_t M, int64_t Mp, float* gar, float* ga_last, float* fbar, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Backward of the radiance network in 'idr' mode (i2sdf_rgb_backward returns I2SDF_EINVAL on such a plan): as above, and in the same
+ * kernel, from G(a_0) while it is in registers,
+ *   nbar_rgb[m] = W_0[:, normal columns]^T G(a_0)[m]      (M,3)  d loss / d normal through the radiance net
+ * accumulate == 0: nbar (M,3) is written ; != 0: nbar_rgb is ADDED to it -- the rows [0, M) of the `nbar` that i2sdf_sdf_backward takes,
+ * after the compositing / loss backward has written them.  One lane owns a point: plain loads and stores, no atomics, deterministic.
+ * The six extra columns of d W_0 come out of i2sdf_weight_grads through the 40-wide pev_save operand.
+ * ---------------------------------------------------------------------------------------------- */
+int i2sdf_rgb_backward_idr(const i2sdf_plan* plan, const float* packed, const float* rgb, const float* rgb_bar, const float* rs,
+                           int64_t M, int64_t Mp, float* gar, float* ga_last, float* fbar, float* nbar, int32_t accumulate, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Backward of the SDF network including the double backward through d sdf/dx (what loss.backward() does through
