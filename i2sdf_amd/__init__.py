@@ -28,7 +28,7 @@ def __getattr__(name):
                 "TsdfVolume", "refuse", "score"):
         from . import mesh
         return getattr(mesh, name)
-    if name in ("psnr", "ssim", "image_stats", "image_metrics", "to_frames", "interpolate_poses", "pixel_grid"):
+    if name in ("psnr", "ssim", "image_stats", "image_metrics", "to_frames", "interpolate_poses", "pixel_grid", "linear_to_srgb"):
         from . import views
         return getattr(views, name)
     if name == "RenderEngine":

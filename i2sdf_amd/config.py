@@ -69,6 +69,8 @@ class NetConfig:
     use_normal: bool = False
     detach_light_feature: bool = True
     rgb_mode: str = "nerf"
+    # rendering_network.output_activation (mlp.py:153-157, 206, 227): 'sigmoid', or 'relu' / 'softplus' for radiance above 1 (HDR targets)
+    rgb_act: str = "sigmoid"
     # arithmetic of the MFMA kernels that have a bf16x3 twin (csrc/x3.h): fp32 operands split into three bf16 terms, six
     # partial products accumulated in fp32 -- fp32-level accuracy (same parity bar) on the 16x faster bf16 matrix pipe.
     # `bf16x3: false` in the model conf selects the plain fp32-MFMA kernels everywhere.
@@ -119,6 +121,14 @@ class NetConfig:
             raise NotImplementedError("hidden widths must be uniform")
         sdf = MlpShape("implicit_network", dims, hid[0], d_in, multires, skip_in[0] if skip_in else -1)
         # --- RenderingNetwork (mlp.py:176-198)
+        if _get(inet, "output_activation", None) is not None:
+            raise NotImplementedError("implicit_network.output_activation: the reference applies it to the whole [sdf | feature] output "
+                                      "(model/network/mlp.py:102-103); no kernel here does, and no shipped config sets it")
+        act = _get(rnet, "output_activation", None)
+        act = "sigmoid" if act is None else act          # (mlp.py:170: the default)
+        if act not in ("sigmoid", "relu", "softplus"):
+            raise NotImplementedError(f"rendering_network.output_activation must be one of 'sigmoid', 'relu', 'softplus' (the reference's "
+                                      f"`activations` table, model/network/mlp.py:153-157, has no other entry); got {act!r}")
         mode = _get(rnet, "mode")
         if mode not in ("nerf", "idr"):
             raise NotImplementedError("rendering_network.mode must be 'nerf' (the shipped configs) or 'idr' (their documented two-line switch)")
@@ -167,7 +177,7 @@ class NetConfig:
                          scene_bounding_sphere=float(_get(conf, "scene_bounding_sphere", 1.0)),
                          beta_init=float(_get(_get(dens, "params_init"), "beta")), beta_min=float(_get(dens, "beta_min", 1e-4)),
                          sdf_bias=float(_get(inet, "bias", 1.0)), use_normal=bool(_get(conf, "use_normal", False)),
-                         detach_light_feature=bool(_get(conf, "detach_light_feature", True)), rgb_mode=mode,
+                         detach_light_feature=bool(_get(conf, "detach_light_feature", True)), rgb_mode=mode, rgb_act=act,
                          bf16x3=bool(_get(conf, "bf16x3", True)), wgrad_bf16x2=bool(_get(conf, "wgrad_bf16x2", True)),
                          sampler_bf16x2=bool(_get(conf, "sampler_bf16x2", True)), saves24=bool(_get(conf, "saves24", True)))
 

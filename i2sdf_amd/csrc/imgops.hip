@@ -36,6 +36,8 @@
 //                           matters for d < 0, where the reference's cast is undefined)
 //                 depth_rgb8 = lut[depth8]                                                          (the caller's colour map)
 //               A NaN becomes 0.
+// linear_to_srgb  (i2sdf_linear_to_srgb) elementwise tone map of HDR validation views (utils/rend_util.py:linear_to_srgb behind an optional clamp to [0, 1]),
+//               one lane per value, in place allowed.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -312,6 +314,16 @@ __global__ __launch_bounds__(IM_THREADS) void im_frames(Frames A) {
   }
 }
 
+// (utils/rend_util.py:linear_to_srgb, optionally behind clamp(0, 1)); a lane reads its element before it writes it: in place is allowed
+__global__ __launch_bounds__(IM_THREADS) void im_linear_to_srgb(const float* src, float* dst, int64_t n, int clamp01) {
+  const int64_t i = (int64_t)blockIdx.x * IM_THREADS + threadIdx.x;
+  if (i >= n) return;
+  float x = src[i];
+  if (clamp01) x = fminf(fmaxf(x, 0.0f), 1.0f);
+  // 1.055 x^(1/2.4) - 0.055 written as 1.055 (x^(1/2.4) - 1) + 1: the same function, and 1 maps to 1 exactly (include/i2sdf.h)
+  dst[i] = x <= 0.0031308f ? x * 12.92f : 1.055f * (powf(x, 1.0f / 2.4f) - 1.0f) + 1.0f;
+}
+
 bool bad_sizes(int32_t n_views, int32_t H, int32_t W, int min_side) {
   return n_views < 0 || n_views > 65535 || H < min_side || W < min_side || (int64_t)H * W > INT32_MAX;
 }
@@ -378,4 +390,13 @@ extern "C" int i2sdf_image_frames(const float* rgb, const float* normal, const f
   const Frames A{rgb, normal, depth, pose, stats, lut, rgb8, normal8, depth8, depth_rgb8, normal_cam, hw};
   im_frames<<<dim3((unsigned)((hw + IM_THREADS - 1) / IM_THREADS), (unsigned)n_views), IM_THREADS, 0, (hipStream_t)stream>>>(A);
   return i2sdf_hip_check(hipGetLastError(), "im_frames");
+}
+
+extern "C" int i2sdf_linear_to_srgb(const float* src, float* dst, int64_t n, int32_t clamp01, void* stream) {
+  if (n < 0) return I2SDF_EINVAL;
+  if (n == 0) return I2SDF_OK;
+  const int64_t blocks = (n + IM_THREADS - 1) / IM_THREADS;
+  if (!src || !dst || blocks > INT32_MAX) return I2SDF_EINVAL;
+  im_linear_to_srgb<<<(unsigned)blocks, IM_THREADS, 0, (hipStream_t)stream>>>(src, dst, n, clamp01 ? 1 : 0);
+  return i2sdf_hip_check(hipGetLastError(), "im_linear_to_srgb");
 }

@@ -53,6 +53,7 @@ struct RgbFwdArgs {
   // 'idr' mode only (include/i2sdf.h: i2sdf_rgb_forward_idr): the side row is [x | PE(view) | normal], pev_save is (Mp, 40)
   i2sdf::PointSpec pts{};               // x of point m
   const float* normals = nullptr;       // (M,3) d sdf/dx as i2sdf_sdf_forward_grad returned it
+  int act = 0;                          // output activation I2SDF_RGB_ACT_* (mlp_common.h: rgb_out_act), wave uniform
 };
 
 struct RgbBwdArgs {
@@ -69,6 +70,7 @@ struct RgbBwdArgs {
   // 'idr' mode only (i2sdf_rgb_backward_idr): d loss / d normal = W_0[:, normal columns]^T G(a_0)
   float* nbar = nullptr;    // (M,3)
   int nbar_acc = 0;         // 0: written, 1: added to what is there
+  int act = 0;              // output activation I2SDF_RGB_ACT_* of the forward (mlp_common.h: rgb_out_act_grad), wave uniform
 };
 
 // bf16x3 kernels: launch over `grid` workgroups of 128 points -- four 32-point waves (mlp_x3.hip: d sdf/dx chain, sweeps) or eight 16-point

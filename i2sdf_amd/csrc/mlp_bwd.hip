@@ -233,8 +233,7 @@ __global__ __launch_bounds__(256) void rgb_bwd_kernel(RgbBwdArgs a) {
   float g3[3];
 #pragma unroll
   for (int j = 0; j < 3; ++j) {
-    const float c = a.rgb[mc * 3 + j];
-    g3[j] = a.rgb_bar[mc * 3 + j] * c * (1.0f - c);
+    g3[j] = rgb_out_act_grad(a.act, a.rgb[mc * 3 + j], a.rgb_bar[mc * 3 + j]);
   }
   if (valid && hi == 0) *reinterpret_cast<f32x4*>(a.ga_last + m * 4) = f32x4{g3[0], g3[1], g3[2], 0.f};
   WStream ws;
@@ -309,8 +308,7 @@ __global__ __launch_bounds__(256) void rgb_bwd_split_kernel(RgbBwdArgs a, int64_
   float g3[3];
 #pragma unroll
   for (int j = 0; j < 3; ++j) {
-    const float c = a.rgb[mc * 3 + j];
-    g3[j] = a.rgb_bar[mc * 3 + j] * c * (1.0f - c);
+    g3[j] = rgb_out_act_grad(a.act, a.rgb[mc * 3 + j], a.rgb_bar[mc * 3 + j]);
   }
   if (valid && hi == 0 && w == 0) *reinterpret_cast<f32x4*>(a.ga_last + m * 4) = f32x4{g3[0], g3[1], g3[2], 0.f};
   WStream ws;
@@ -423,6 +421,7 @@ extern "C" int i2sdf_rgb_backward(const i2sdf_plan* p, const float* packed, cons
   RgbBwdArgs a{};
   a.rev = rev.w; a.n_rev = rev.n_stages;
   a.L = d.n_lin; a.M = M; a.Mp = Mp; a.rgb = rgb; a.rgb_bar = rgb_bar; a.rs = rs; a.gar = gar; a.ga_last = ga_last; a.fbar = fbar;
+  a.act = rgb_act(d);
   RgbBwdArgs a3 = a;
   if (x3) {                                           // 16-point waves (x3h.h)
     const Span rev3 = span(p, packed, p->rgb, SPAN_REV3H);
@@ -463,6 +462,7 @@ extern "C" int i2sdf_rgb_backward_idr(const i2sdf_plan* p, const float* packed, 
   RgbBwdArgs a{};
   a.rev = rev.w; a.n_rev = rev.n_stages;
   a.L = d.n_lin; a.M = M; a.Mp = Mp; a.rgb = rgb; a.rgb_bar = rgb_bar; a.rs = rs; a.gar = gar; a.ga_last = ga_last; a.fbar = fbar;
+  a.act = rgb_act(d);
   a.nbar = nbar; a.nbar_acc = accumulate ? 1 : 0;
   if (x3) a.kcs = rgb_blocked_points(p, M, Mp) > 0 ? KCS_BLK : KCS_PM;
   hipStream_t st = (hipStream_t)stream;

@@ -78,6 +78,25 @@ inline int64_t rgb_blocked_points(const i2sdf_plan* p, int64_t M, int64_t Mp) {
 
 constexpr float RS2 = 0.70710678118654752440f;
 
+// ---- output activation of the radiance net (rendering_network.output_activation, mlp.py:153-157, 227; I2SDF_RGB_ACT_*) --------------
+// `act` is a kernel argument, the same for every lane.  The backward kernels have the saved output y and nothing else: the derivative is
+// recovered from it.
+//   sigmoid   y = 1 / (1 + e^-o)                           dy/do = y (1 - y)   (the expressions every plan had before the option existed)
+//   relu      y = max(o, 0)                                dy/do = y > 0       (torch's rule: 0 at the kink)
+//   softplus  y = o > 20 ? o : log1p(e^o)  (nn.Softplus)   dy/do = y > 20 ? 1 : -expm1(-y): sigmoid(o) = 1 - e^-y exactly, and y <= 20
+//             whenever o <= 20 in fp32 (log1p(e^20) rounds to 20); expm1 keeps the relative accuracy where y is tiny
+__device__ __forceinline__ float rgb_out_act(int act, float o) {
+  if (act == I2SDF_RGB_ACT_RELU) return fmaxf(o, 0.f);
+  if (act == I2SDF_RGB_ACT_SOFTPLUS) return o > 20.f ? o : log1pf(expf(o));
+  return 1.0f / (1.0f + expf(-o));
+}
+// G(a_last) = rgb_bar * dy/do from the saved output y
+__device__ __forceinline__ float rgb_out_act_grad(int act, float y, float ybar) {
+  if (act == I2SDF_RGB_ACT_RELU) return y > 0.f ? ybar : 0.f;
+  if (act == I2SDF_RGB_ACT_SOFTPLUS) return y > 20.f ? ybar : ybar * -expm1f(-y);
+  return ybar * y * (1.0f - y);
+}
+
 template <int N>
 __device__ __forceinline__ void softplus_tiles(const f32x16 (&acc)[N], float (&h)[N * 16]) {
 #pragma unroll

@@ -292,7 +292,7 @@ __global__ __launch_bounds__(256) void rgb_fwd_kernel(RgbFwdArgs a) {
   rowvec_op<3, KC>(ws, r, o, tid);
   if (valid && hi == 0) {
 #pragma unroll
-    for (int i = 0; i < 3; ++i) a.rgb[m * 3 + i] = 1.0f / (1.0f + expf(-o[i]));
+    for (int i = 0; i < 3; ++i) a.rgb[m * 3 + i] = rgb_out_act(a.act, o[i]);
   }
 }
 
@@ -347,7 +347,7 @@ __global__ __launch_bounds__(256) void rgb_fwd_split_kernel(RgbFwdArgs a, int64_
   rowvec_ksplit<3>(ws, rq, o, slds, tid);
   if (valid && hi == 0 && w == 0) {
 #pragma unroll
-    for (int i = 0; i < 3; ++i) a.rgb[m * 3 + i] = 1.0f / (1.0f + expf(-o[i]));
+    for (int i = 0; i < 3; ++i) a.rgb[m * 3 + i] = rgb_out_act(a.act, o[i]);
   }
 }
 
@@ -436,6 +436,7 @@ extern "C" int i2sdf_rgb_forward(const i2sdf_plan* p, const float* packed, const
   RgbFwdArgs a{};
   a.fwd = fwd.w; a.n_fwd = fwd.n_stages;
   a.L = d.n_lin; a.dirs = dirs; a.n_per_ray = n_per_ray; a.feat = feat; a.M = M; a.Mp = Mp; a.rgb = rgb; a.rs = rs; a.pev_save = pev_save;
+  a.act = rgb_act(d);
   // full workgroups optionally in bf16x3 split arithmetic (mlp_x3h.hip); the split-K tail keeps the fp32 MFMA kernel
   RgbFwdArgs a3 = a;
   if (x3) {
@@ -480,6 +481,7 @@ extern "C" int i2sdf_rgb_forward_idr(const i2sdf_plan* p, const float* packed, c
   RgbFwdArgs a{};
   a.fwd = fwd.w; a.n_fwd = fwd.n_stages;
   a.L = d.n_lin; a.dirs = dirs; a.n_per_ray = n_per_ray; a.feat = feat; a.M = M; a.Mp = Mp; a.rgb = rgb; a.rs = rs; a.pev_save = pev_save;
+  a.act = rgb_act(d);
   a.pts = PointSpec{points, cam, dirs, z, ldz, points ? 0 : M, n_per_ray};
   a.normals = normals;
   if (x3) a.kcs = rgb_blocked_points(p, M, Mp) > 0 ? KCS_BLK : KCS_PM;

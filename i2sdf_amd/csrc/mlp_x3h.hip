@@ -191,7 +191,7 @@ __global__ __launch_bounds__(NW * 64, 2) void rgb_fwd3h_kernel(RgbFwdArgs a) {
   rowvec_h<3, NT, NW>(ws, r, o, tid);
   if (valid && kg == 0) {
 #pragma unroll
-    for (int i = 0; i < 3; ++i) a.rgb[m * 3 + i] = 1.0f / (1.0f + expf(-o[i]));
+    for (int i = 0; i < 3; ++i) a.rgb[m * 3 + i] = rgb_out_act(a.act, o[i]);
   }
 }
 
@@ -237,8 +237,7 @@ __global__ __launch_bounds__(NW * 64, 2) void rgb_bwd3h_kernel(RgbBwdArgs a) {
   float g3[3];
 #pragma unroll
   for (int j = 0; j < 3; ++j) {
-    const float c = a.rgb[mc * 3 + j];
-    g3[j] = a.rgb_bar[mc * 3 + j] * c * (1.0f - c);
+    g3[j] = rgb_out_act_grad(a.act, a.rgb[mc * 3 + j], a.rgb_bar[mc * 3 + j]);
   }
   if (valid && kg == 0) *reinterpret_cast<f32x4*>(a.ga_last + m * 4) = f32x4{g3[0], g3[1], g3[2], 0.f};
   WStreamH<NW> ws;

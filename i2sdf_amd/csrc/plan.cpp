@@ -228,7 +228,8 @@ int build_rgb(i2sdf_plan* p, Builder& b) {
   const bool idr = rgb_idr(d);
   const int L = d.n_lin, H = d.hidden, PED = pe_dim(d), PEC = cdiv(PED, 8), F = p->F;
   if (check_mlp(d)) return I2SDF_EINVAL;
-  if ((d.reserved != I2SDF_RGB_MODE_NERF && !idr) || (idr && d.d_in != 9)) return I2SDF_EINVAL;
+  if ((rgb_mode(d) != I2SDF_RGB_MODE_NERF && !idr) || (idr && d.d_in != 9)) return I2SDF_EINVAL;
+  if (rgb_act(d) > I2SDF_RGB_ACT_SOFTPLUS || (d.reserved & ~0xffff)) return I2SDF_EINVAL;      // (i2sdf_plan_create says why)
   // the reverse product of layer 0: the feature rows of W_0^T; 'idr' adds one more tile behind them that holds the three normal rows
   const ColMap rev0 = idr ? ColMap{F, PED, F, PED - 3, 3} : ColMap{HUGE_SPLIT, PED, F, 0, 0};
   if (d.skip_layer >= 0 || d.d_out != 3 || (d.multires <= 0 && !idr) || d.in0 != PED + F || F <= 0) return I2SDF_EINVAL;
@@ -326,6 +327,12 @@ extern "C" int i2sdf_plan_create(const i2sdf_net_desc* desc, i2sdf_plan** out) {
     }
     if (rgb_idr(desc->rgb) && desc->rgb.d_in != 9) {
       g_hip_err = "i2sdf_plan_create: the radiance net's 'idr' mode needs d_in 9 (points, view directions, normals)";
+      return I2SDF_EINVAL;
+    }
+    if (rgb_act(desc->rgb) > I2SDF_RGB_ACT_SOFTPLUS || (desc->rgb.reserved & ~0xffff)) {
+      g_hip_err = "i2sdf_plan_create: rgb.reserved " + std::to_string(desc->rgb.reserved) + ": output activation " + std::to_string(rgb_act(desc->rgb)) +
+                  " of the radiance net is not one of I2SDF_RGB_ACT_SIGMOID (0), I2SDF_RGB_ACT_RELU (1), I2SDF_RGB_ACT_SOFTPLUS (2) in bits 8..15"
+                  " (bits 16 and up must be zero)";
       return I2SDF_EINVAL;
     }
   }

@@ -71,7 +71,10 @@ constexpr SpanId SPAN_FWD2H{FWD2H, FWD2H_END, SCH};
 // [x | PE(view) | normal] (include/i2sdf.h: I2SDF_RGB_MODE_*), one contiguous block of lin0.weight_v in either mode
 // side_dim: THE width of a net's encoded input in front of the hidden / feature columns of its layer 0 -- PE(x) of the SDF net, the side row
 // of the radiance net, d_in of a net without encoding (plan.cpp, wgrad.hip and the launch sites all take it from here)
-inline bool rgb_idr(const i2sdf_mlp_desc& d) { return d.reserved == I2SDF_RGB_MODE_IDR; }
+// reserved = mode | act << 8 (include/i2sdf.h): the mode in bits 0..7, the output activation I2SDF_RGB_ACT_* in bits 8..15
+inline int rgb_mode(const i2sdf_mlp_desc& d) { return d.reserved & 0xff; }
+inline int rgb_act(const i2sdf_mlp_desc& d) { return (d.reserved >> 8) & 0xff; }
+inline bool rgb_idr(const i2sdf_mlp_desc& d) { return rgb_mode(d) == I2SDF_RGB_MODE_IDR; }
 inline int side_dim(const i2sdf_mlp_desc& d) {
   const int raw = rgb_idr(d) ? 3 : d.d_in;          // 'idr': only the view direction (3 of the 9 raw inputs) is encoded
   return (d.multires > 0 ? raw + 2 * raw * d.multires : raw) + (rgb_idr(d) ? 6 : 0);

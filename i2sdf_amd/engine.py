@@ -377,6 +377,12 @@ class RenderEngine:
         """rendering_network.mode == 'idr': the radiance net also takes the points and the normals (include/i2sdf.h: I2SDF_RGB_MODE_IDR)"""
         return self.cfg.rgb_mode == "idr"
 
+    @property
+    def rgb_act(self) -> str:
+        """rendering_network.output_activation: 'sigmoid', 'relu' or 'softplus' -- the plan carries it (include/i2sdf.h: I2SDF_RGB_ACT_*), so
+        rgb_forward / rgb_backward, render_image and both loss routes take it from there; `rgb` may exceed 1 with the last two"""
+        return self.cfg.rgb_act
+
     def rgb_forward(self, dirs, n_per_ray, feat, M, save=True, fw=None, points=None, normals=None):
         """'idr' mode needs the points and normals of the M points: `fw`, the dict of the sdf_forward_grad call that produced `feat` (its
         leading M points are ray samples), or explicit `points` (M,3) and `normals` (M,3).  `pev` is the saved side row: (Mp,32) PE(view)

@@ -76,7 +76,8 @@ OPT_SAMPLER_BF16X2 = 1024
 OPT_SAVES24 = 2048
 MAX_PARTS = 4
 GRID_ORDER_MESHGRID, GRID_ORDER_VOLUME = 0, 1
-RGB_MODE_NERF, RGB_MODE_IDR = 0, 1    # I2SDF_RGB_MODE_*: i2sdf_net_desc.rgb.reserved
+RGB_MODE_NERF, RGB_MODE_IDR = 0, 1    # I2SDF_RGB_MODE_*: i2sdf_net_desc.rgb.reserved, bits 0..7
+RGB_ACTS = {"sigmoid": 0, "relu": 1, "softplus": 2}      # I2SDF_RGB_ACT_*: the same field, bits 8..15 (reserved = mode | act << 8)
 RASTER_SMALL_MAX = 64            # I2SDF_RASTER_SMALL_MAX
 TSDF_MAX_CELLS = 1 << 24         # I2SDF_TSDF_MAX_CELLS
 IMAGE_STATS = 8                  # I2SDF_IMAGE_STATS
@@ -216,6 +217,8 @@ SIGNATURES = {
     "i2sdf_image_ssim": (C.c_int, [_P, _P, _I32, _I32, _I32, _F, _P, _P, _P, _P, _P]),
     # rgb, normal, depth, pose, stats, lut, n_views, H, W, rgb8, normal8, normal_cam, depth8, depth_rgb8, stream
     "i2sdf_image_frames": (C.c_int, [_P] * 6 + [_I32, _I32, _I32] + [_P] * 6),
+    # src, dst, n, clamp01, stream
+    "i2sdf_linear_to_srgb": (C.c_int, [_P, _P, _I64, _I32, _P]),
     # pred, target, channels, pixel_idx, first_pixel, n, pointlinks, n_links, pdf_max, pdf_prune, pdf, n_pdf, n_bad, stream
     "i2sdf_pdf_update": (C.c_int, [_P, _P, _I32, _P, _I64, _I64, _P, _I64, C.c_double, C.c_double, _P, _I64, _P, _P]),
     # seed, B, n_eval, n_samples, n_extra, max_iters, n_z, eik_radius, nbr_half_width, strat_u, cdf_u, extra_idx, eik_idx, eik_pts, nbr_off, stream

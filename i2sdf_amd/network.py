@@ -71,9 +71,10 @@ class ImplicitNetwork(_Mlp):
 
 
 class RenderingNetwork(_Mlp):
-    def __init__(self, shape: MlpShape, mode: str):
+    def __init__(self, shape: MlpShape, mode: str, output_activation: str = "sigmoid"):
         super().__init__(shape)
         self.mode = mode
+        self.output_activation = output_activation      # 'sigmoid' | 'relu' | 'softplus' (no parameters: the state_dict does not change)
 
 
 class LaplaceDensity(nn.Module):
@@ -319,7 +320,7 @@ class I2SDFNetwork(nn.Module):
         self.feature_vector_size = cfg.feature_size
         self.scene_bounding_sphere = cfg.scene_bounding_sphere
         self.implicit_network = ImplicitNetwork(cfg.sdf, self)
-        self.rendering_network = RenderingNetwork(cfg.rgb, cfg.rgb_mode)
+        self.rendering_network = RenderingNetwork(cfg.rgb, cfg.rgb_mode, cfg.rgb_act)
         self.use_light = cfg.light is not None
         if self.use_light:
             self.light_network = _Mlp(cfg.light)
@@ -552,7 +553,7 @@ class I2SDFNetwork(nn.Module):
     @torch.no_grad()
     def evaluate_views(self, poses: torch.Tensor, intrinsics: torch.Tensor, img_res, gt_rgb: Optional[torch.Tensor] = None,
                        split_n_pixels: int = 12000, frames: bool = False, lut: Optional[torch.Tensor] = None,
-                       keep_outputs: bool = True, _frame_inputs=("rgb", "normal", "depth")) -> Dict[str, torch.Tensor]:
+                       keep_outputs: bool = True, _frame_inputs=("rgb", "normal", "depth"), hdr: bool = False) -> Dict[str, torch.Tensor]:
         """A test sweep with everything on the device: the per-view loop of VolumeRenderSystem.test_step / ViewInterpolateSystem.test_step
         (model/eval/recon.py:161-203, :257-281) around `render_image`, its metrics and its frames.  `poses` (n, 4, 4) camera-to-world,
         `intrinsics` (4, 4) or (n, 4, 4), `img_res` (H, W); every view is rendered over i2sdf_amd.views.pixel_grid(H, W) in chunks of
@@ -562,6 +563,8 @@ class I2SDFNetwork(nn.Module):
                   (views.to_frames)
           keep_outputs: adds "rgb_values" (n, H W, 3), "depth_values" (n, H W, 1), "normal_map" (n, H W, 3), "weight_sum" (n, H W, 1).
                         False: one view's buffers are reused and the metrics / frames are taken view by view (the same numbers).
+          hdr: the data set is HDR (`is_hdr: True`; model/trainer/recon.py:320-350): "psnr", "ssim" and "rgb8" come from
+               views.linear_to_srgb(x.clamp(0, 1)) of the render and of gt_rgb; "rgb_values" stays the raw render (the reference's `hdr_eval`).
         "sampler_iters" (n, n_chunks) int32: the sampler's iteration count per view and chunk.  All results stay on the device;
         nothing in here waits for it -- the caller's first read of a result is the only host synchronisation."""
         from . import views as V
@@ -592,11 +595,11 @@ class I2SDFNetwork(nn.Module):
         def finish(sl, lo, hi):
             r = {}
             if gt is not None:
-                r.update(V.image_metrics(buf["rgb"][sl], gt[lo:hi], (H, W)))
+                r.update(V.image_metrics(buf["rgb"][sl], gt[lo:hi], (H, W), hdr=hdr))
             if frames:
                 src = {k: buf[k][sl] if k in _frame_inputs else None for k in ("rgb", "normal", "depth")}
                 r.update(V.to_frames(rgb=src["rgb"], normal_map=src["normal"], depth=src["depth"], pose=poses[lo:hi], img_res=(H, W),
-                                     lut=lut))
+                                     lut=lut, hdr=hdr))
             return r
 
         with torch.cuda.device(dev):

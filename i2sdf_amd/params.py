@@ -8,7 +8,7 @@ import numpy as np
 import torch
 
 from .config import MlpShape, NetConfig
-from .lib import MAX_LAYERS, RGB_MODE_IDR, RGB_MODE_NERF, MlpDesc, NetDesc
+from .lib import MAX_LAYERS, RGB_ACTS, RGB_MODE_IDR, RGB_MODE_NERF, MlpDesc, NetDesc
 
 
 class ParamLayout:
@@ -54,7 +54,7 @@ class ParamLayout:
         nd = NetDesc()
         nd.sdf = self._mlp_desc(c.sdf, c.sdf.dims[-1][0])
         nd.rgb = self._mlp_desc(c.rgb, c.rgb.dims[-1][0])
-        nd.rgb.reserved = RGB_MODE_IDR if c.rgb_mode == "idr" else RGB_MODE_NERF
+        nd.rgb.reserved = (RGB_MODE_IDR if c.rgb_mode == "idr" else RGB_MODE_NERF) | RGB_ACTS[c.rgb_act] << 8
         if c.light is not None:
             nd.light = self._mlp_desc(c.light, 1)
         nd.off_beta = self.offset("density.beta")

@@ -3,6 +3,11 @@ does with a finished view -- PSNR and SSIM (model/eval/recon.py:197-201), the ca
 8-bit frames its writers get (utils/plots.py:492-506, :538-555; recon.py:272-273) and the camera path of a view interpolation
 (dataset/eval_dataset.py:213-241).
 
+HDR data (`is_hdr: True`): the reference tone-maps prediction and ground truth with `rend_util.linear_to_srgb(x.clamp(0, 1))` before the
+metrics and the 8-bit images and keeps the raw values beside them (model/trainer/recon.py:320-350): `linear_to_srgb`, and `hdr=True` of
+`psnr` / `ssim` / `image_metrics` / `to_frames`, which run it into a scratch stack first -- the same kernels then see the same numbers as
+after an explicit `linear_to_srgb` call, bit for bit.
+
 Images keep the render outputs' layout: (H W, C) or (n_views, H W, C) fp32 on the device, pixel p = y W + x; `img_res` = (H, W).
 There is no CPU path: a CPU tensor raises ValueError before the library is loaded.  Nothing here synchronises with the host.
 
@@ -95,6 +100,32 @@ def _ssim_of(lib, pred, gt, n, H, W, data_range, stats, ws, return_map):
 
 
 @torch.no_grad()
+def linear_to_srgb(x, clamp: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """utils/rend_util.py:linear_to_srgb on the device, elementwise, any shape: x <= 0.0031308 ? 12.92 x : 1.055 x^(1/2.4) - 0.055, with
+    `clamp` (the default: what the reference's validation does with HDR images) on clamp(x, 0, 1).  0 maps to 0 and, clamped, everything
+    from 1 up to 1, exactly.  Returns a new fp32 tensor, or `out` (same shape, contiguous fp32, same device; `out is x` tone-maps in place)."""
+    if not torch.is_tensor(x) or not x.is_cuda:
+        raise ValueError("linear_to_srgb: x must be a tensor on a GPU (there is no CPU path)")
+    if x.dtype != torch.float32:
+        raise ValueError(f"linear_to_srgb: x must be float32, got {x.dtype}")
+    src = x.detach().contiguous()
+    if out is None:
+        out = torch.empty_like(src)
+    elif not torch.is_tensor(out) or out.shape != x.shape or out.dtype != torch.float32 or out.device != x.device or not out.is_contiguous():
+        raise ValueError("linear_to_srgb: out must be a contiguous float32 tensor of x's shape on x's device")
+    if src.numel():
+        with torch.cuda.device(src.device):
+            L.check(L.load().i2sdf_linear_to_srgb(L.ptr(src), L.ptr(out), src.numel(), int(bool(clamp)), L.stream_ptr()),
+                    "i2sdf_linear_to_srgb")
+    return out
+
+
+def _tone(hdr, *imgs):
+    """the images as the metrics and frames see them: tone-mapped copies (clamped, as get_plot_data does) with `hdr`, else as they are"""
+    return tuple(linear_to_srgb(t, True) if (hdr and t is not None) else t for t in imgs)
+
+
+@torch.no_grad()
 def image_stats(pred, gt, img_res, depth=None) -> torch.Tensor:
     """(n, 8) fp64 device: [0] sum over the 3 H W values of (pred - gt)^2 in fp64, [1:3] min, max of pred, [3:5] min, max of gt,
     [5] max of `depth` (-inf without one).  One pass; bitwise reproducible."""
@@ -111,20 +142,25 @@ def image_stats(pred, gt, img_res, depth=None) -> torch.Tensor:
 
 
 @torch.no_grad()
-def psnr(pred, gt, img_res) -> torch.Tensor:
+def psnr(pred, gt, img_res, hdr: bool = False) -> torch.Tensor:
     """(n,) fp64 device: -10 log10(mean((pred - gt)^2)) per view (utils/rend_util.py:get_psnr, which takes the mean in fp32; here the
-    differences, squares and sums are fp64).  +inf for identical images, as in the reference.  Any size from 1 x 1."""
+    differences, squares and sums are fp64).  +inf for identical images, as in the reference.  Any size from 1 x 1.
+    hdr: of linear_to_srgb(clamp(., 0, 1)) of both images."""
     H, W = _res(img_res, "psnr")
-    return _psnr_of(image_stats(pred, gt, img_res), H, W)
+    p, g, _, _ = _pair(pred, gt, img_res, "psnr")
+    p, g = _tone(hdr, p, g)
+    return _psnr_of(image_stats(p, g, img_res), H, W)
 
 
 @torch.no_grad()
-def ssim(pred, gt, img_res, data_range: Optional[float] = None, return_map: bool = False):
+def ssim(pred, gt, img_res, data_range: Optional[float] = None, return_map: bool = False, hdr: bool = False):
     """(n,) fp64 device: the SSIM of torchmetrics 0.11.4 with the reference's defaults (Gaussian window of 11 taps, sigma 1.5), per
     view -- the definition is written out in include/i2sdf.h.  `data_range` None: max(max pred - min pred, max gt - min gt) of each
     view, taken on the device (what torchmetrics does for the one-view batch the reference passes).  H, W >= 11.
-    return_map: also the (n, H - 10, W - 10, 3) fp32 per-pixel values; the mean is bit-identical either way."""
+    return_map: also the (n, H - 10, W - 10, 3) fp32 per-pixel values; the mean is bit-identical either way.
+    hdr: of linear_to_srgb(clamp(., 0, 1)) of both images."""
     p, g, H, W = _pair(pred, gt, img_res, "ssim", SSIM_WINDOW)
+    p, g = _tone(hdr, p, g)
     r = _data_range(data_range, "ssim")
     n, dev = p.shape[0], p.device
     if n == 0:
@@ -139,10 +175,12 @@ def ssim(pred, gt, img_res, data_range: Optional[float] = None, return_map: bool
 
 
 @torch.no_grad()
-def image_metrics(pred, gt, img_res, data_range: Optional[float] = None) -> dict:
+def image_metrics(pred, gt, img_res, data_range: Optional[float] = None, hdr: bool = False) -> dict:
     """{"psnr": (n,) fp64, "ssim": (n,) fp64} on the device: one stats pass serves both (the squared error for PSNR, the value range
-    for SSIM).  H, W >= 11."""
+    for SSIM).  H, W >= 11.  hdr: both images go through linear_to_srgb(clamp(., 0, 1)) first (model/trainer/recon.py: get_plot_data
+    with is_hdr); bit-identical to image_metrics(linear_to_srgb(pred), linear_to_srgb(gt), ...)."""
     p, g, H, W = _pair(pred, gt, img_res, "image_metrics", SSIM_WINDOW)
+    p, g = _tone(hdr, p, g)
     r = _data_range(data_range, "image_metrics")
     n, dev = p.shape[0], p.device
     if n == 0:
@@ -157,9 +195,11 @@ def image_metrics(pred, gt, img_res, data_range: Optional[float] = None) -> dict
 
 
 @torch.no_grad()
-def to_frames(rgb=None, normal_map=None, depth=None, pose=None, img_res=None, lut=None, camera_normals: bool = False) -> dict:
+def to_frames(rgb=None, normal_map=None, depth=None, pose=None, img_res=None, lut=None, camera_normals: bool = False,
+              hdr: bool = False) -> dict:
     """The 8-bit images the reference hands to its writers, as uint8 device tensors (n, H, W, C); a key per input given:
       "rgb8"        trunc(clip(rgb * 255, 0, 255))                                     (plots.py:500-501, recon.py:273)
+                    hdr=True: of linear_to_srgb(clamp(rgb, 0, 1)); the other frames do not change
       "normal8"     from the WORLD-space `normal_map` and `pose` ((4, 4) or (n, 4, 4), camera-to-world): n_cam = pose[:3, :3]^T n
                     (recon.py:184-186), then trunc(clip((n_cam + 1) / 2 * 255, 0, 255)); camera_normals=True adds "normal_cam",
                     the fp32 (n, H W, 3) map the reference writes as .exr
@@ -168,6 +208,7 @@ def to_frames(rgb=None, normal_map=None, depth=None, pose=None, img_res=None, lu
     H, W = _res(img_res, "to_frames")
     hw = H * W
     r = None if rgb is None else _stack(rgb, hw, 3, "to_frames", "rgb")
+    r, = _tone(hdr, r)
     nm = None if normal_map is None else _stack(normal_map, hw, 3, "to_frames", "normal_map")
     d = None if depth is None else _stack(depth, hw, 1, "to_frames", "depth")
     given = [t for t in (r, nm, d) if t is not None]

@@ -50,7 +50,7 @@ typedef struct i2sdf_mlp_desc {
   int32_t d_out;                          /* rows of the last layer                                  */
   int32_t multires;                       /* positional-encoding frequencies L (embedder.py:138-152) */
   int32_t skip_layer;                     /* l with `l in skip_in` (mlp.py:94), -1 if none           */
-  int32_t reserved;                       /* radiance net: I2SDF_RGB_MODE_* (0 = 'nerf'); 0 for the other nets */
+  int32_t reserved;                       /* radiance net: I2SDF_RGB_MODE_* | I2SDF_RGB_ACT_* << 8 (0 = 'nerf', sigmoid); 0 for the other nets */
   int32_t out_dim[I2SDF_MAX_LAYERS];      /* rows of weight_v per layer                              */
   int32_t in_dim[I2SDF_MAX_LAYERS];       /* cols of weight_v per layer                              */
   int64_t off_bias[I2SDF_MAX_LAYERS];
@@ -66,10 +66,22 @@ typedef struct i2sdf_mlp_desc {
  * d_in has to agree with the mode; i2sdf_plan_create refuses anything else. */
 #define I2SDF_RGB_MODE_NERF 0
 #define I2SDF_RGB_MODE_IDR 1
+/* rendering_network.output_activation (mlp.py:153-157, 206, 227), the last operation of the radiance net, in bits 8..15 of the same field:
+ * rgb.reserved = I2SDF_RGB_MODE_* | I2SDF_RGB_ACT_* << 8.  A descriptor written before the activations existed (bits 8..15 zero) keeps its
+ * meaning: sigmoid.  With o the output of the last linear layer and y the value the forward entry points write to `rgb`:
+ *   I2SDF_RGB_ACT_SIGMOID   y = 1 / (1 + exp(-o))                                 dy/do = y (1 - y)
+ *   I2SDF_RGB_ACT_RELU      y = max(o, 0): radiance above 1 (HDR targets)         dy/do = y > 0 (0 at the kink, as torch)
+ *   I2SDF_RGB_ACT_SOFTPLUS  y = o > 20 ? o : log1p(exp(o))  (nn.Softplus())       dy/do = y > 20 ? 1 : -expm1(-y)  (= sigmoid(o), exactly)
+ * The backward entry points recover dy/do from the saved `rgb` alone; no further tensor is saved.  The packed weights, the state_dict and
+ * every workspace are the same for the three.  i2sdf_plan_create refuses any other value (and any bit above 15) with I2SDF_EINVAL and a
+ * text in i2sdf_last_hip_error().  Nothing behind the radiance net assumes rgb <= 1 (compositing and the rgb loss are linear in it). */
+#define I2SDF_RGB_ACT_SIGMOID 0
+#define I2SDF_RGB_ACT_RELU 1
+#define I2SDF_RGB_ACT_SOFTPLUS 2
 
 typedef struct i2sdf_net_desc {
   i2sdf_mlp_desc sdf;                     /* ImplicitNetwork: PE(x) -> softplus100 stack -> [sdf | feature]   */
-  i2sdf_mlp_desc rgb;                     /* RenderingNetwork: [side row | feature] -> ReLU -> sigmoid        */
+  i2sdf_mlp_desc rgb;                     /* RenderingNetwork: [side row | feature] -> ReLU -> output act.    */
   i2sdf_mlp_desc light;                   /* light-mask head (n_lin == 0 when absent)                         */
   int64_t off_beta;                       /* density.beta                                                     */
   int64_t n_params;                       /* total floats in `params`                                         */
@@ -221,7 +233,8 @@ int i2sdf_sdf_forward_grad(const i2sdf_plan* plan, const float* packed, const fl
 
 /* ------------------------------------------------------------------------------------------------
  * Radiance network forward, 'nerf' mode -- RenderingNetwork.forward (mlp.py:208-229):
- * rgb = sigmoid(MLP([PE4(view_dir) | feature])).  dirs (B,3) unit view directions, point m uses dirs[m / n_per_ray].
+ * rgb = act(MLP([PE4(view_dir) | feature])), act = the plan's I2SDF_RGB_ACT_* (sigmoid unless the descriptor says otherwise).
+ * dirs (B,3) unit view directions, point m uses dirs[m / n_per_ray].
  *   rgb (M,3) ; rs (L-1, Mp, H) post-ReLU activations and pev_save (Mp,32) PE(view) (NULL if no backward follows)
  * ---------------------------------------------------------------------------------------------- */
 int i2sdf_rgb_forward(const i2sdf_plan* plan, const float* packed, const float* dirs, int32_t n_per_ray, const float* feat,
@@ -229,7 +242,7 @@ int i2sdf_rgb_forward(const i2sdf_plan* plan, const float* packed, const float* 
 
 /* ------------------------------------------------------------------------------------------------
  * Radiance network forward, 'idr' mode (mlp.py:208-216; a plan whose rgb.reserved is I2SDF_RGB_MODE_IDR -- i2sdf_rgb_forward returns
- * I2SDF_EINVAL on such a plan, this entry point on a 'nerf' plan): rgb = sigmoid(MLP([x | PE4(view_dir) | normal | feature])).
+ * I2SDF_EINVAL on such a plan, this entry point on a 'nerf' plan): rgb = act(MLP([x | PE4(view_dir) | normal | feature])).
  * The 33-wide side row [x | PE(view) | normal] is assembled per point in registers:
  *   x       points (M,3) when given, else cam[r] + z[r*ldz + j] * dirs[r] with r = m / n_per_ray, j = m % n_per_ray (as i2sdf_sdf_forward_grad)
  *   view    dirs[m / n_per_ray], as in 'nerf' mode
@@ -246,7 +259,7 @@ int i2sdf_rgb_forward_idr(const i2sdf_plan* plan, const float* packed, const flo
 
 /* ------------------------------------------------------------------------------------------------
  * Backward of the radiance network (autograd through mlp.py:208-229).
- *   rgb (M,3) forward output, rgb_bar (M,3) upstream, rs from the forward
+ *   rgb (M,3) forward output, rgb_bar (M,3) upstream, rs from the forward; G(a_{L-1}) = rgb_bar * dy/do of the plan's I2SDF_RGB_ACT_*, from rgb
  *   -> gar (L-1, Mp, H) G(a_l) l=0..L-2 ; ga_last (Mp,4) G(a_{L-1}) ; fbar (Mp,F) d loss / d feature
  * ---------------------------------------------------------------------------------------------- */
 int i2sdf_rgb_backward(const i2sdf_plan* plan, const float* packed, const float* rgb, const float* rgb_bar, const float* rs,
@@ -865,6 +878,18 @@ int i2sdf_image_ssim(const float* pred, const float* gt, int32_t n_views, int32_
 int i2sdf_image_frames(const float* rgb, const float* normal, const float* depth, const float* pose, const double* stats,
                        const uint8_t* lut, int32_t n_views, int32_t H, int32_t W, uint8_t* rgb8, uint8_t* normal8, float* normal_cam,
                        uint8_t* depth8, uint8_t* depth_rgb8, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Tone map of HDR validation views (csrc/imgops.hip), elementwise over n fp32 values of any layout.  Named outside the i2sdf_image_*
+ * family: it takes no (n_views, H, W) and no workspace.
+ *   dst[i] = srgb(clamp01 ? min(max(src[i], 0), 1) : src[i]) for i < n, srgb(x) = x <= 0.0031308 ? 12.92 x :
+ * 1.055 x^(1/2.4) - 0.055 (utils/rend_util.py:linear_to_srgb; the validation of HDR data tone-maps prediction and ground truth
+ * as `linear_to_srgb(x.clamp(0, 1))` before the metrics and the 8-bit images, model/trainer/recon.py:320-350).  fp32, every
+ * product and sum rounded on its own; the upper branch is evaluated as 1.055 (x^(1/2.4) - 1) + 1, the same function, so that
+ * 0 maps to 0 and 1 to 1 exactly (the formula as written gives 1 - 2^-24 at 1 in fp32, 254 instead of 255 in an 8-bit image).  Any n >= 0 (0: nothing is launched); dst == src (in place) is allowed, any other
+ * overlap is not.  Without clamp01 a negative x takes the linear branch and a NaN stays a NaN; with it a NaN becomes 0.
+ * ---------------------------------------------------------------------------------------------- */
+int i2sdf_linear_to_srgb(const float* src, float* dst, int64_t n, int32_t clamp01, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Bubble-PDF update (row N4) -- VolumeRenderSystem.update_pdf fused with the error it is fed (model/trainer/recon.py:142-152,
