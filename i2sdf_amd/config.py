@@ -29,6 +29,15 @@ class MlpShape:
     d_in: int
     multires: int
     skip_layer: int = -1
+    # rendering_network.embed_type (embedder.py:138-160): 'positional' (multires above; 0 = none), or 'spherical_harmonics' / 'fourier' with
+    # their parameter -- the degree (1..5) or the channel count (1..12); multires is then 0
+    embed: str = "positional"
+    embed_n: int = 0
+
+    @property
+    def embed_dim(self):
+        """width of the embedded view direction of a radiance net with an SH / Fourier embedder"""
+        return self.embed_n ** 2 if self.embed == "spherical_harmonics" else 2 * self.embed_n + 3
 
     @property
     def n_lin(self):
@@ -39,6 +48,8 @@ class MlpShape:
         """width of the encoded input in front of the hidden / feature columns of layer 0 (csrc/plan.h: side_dim); a radiance net in 'idr'
         mode (d_in 9) encodes only the view direction: [x | PE(view) | normal]"""
         raw = 3 if self.d_in == 9 else self.d_in
+        if self.embed != "positional":
+            return self.embed_dim + (self.d_in - raw)
         return (raw + 2 * raw * self.multires if self.multires > 0 else raw) + (self.d_in - raw)
 
 
@@ -71,6 +82,8 @@ class NetConfig:
     rgb_mode: str = "nerf"
     # rendering_network.output_activation (mlp.py:153-157, 206, 227): 'sigmoid', or 'relu' / 'softplus' for radiance above 1 (HDR targets)
     rgb_act: str = "sigmoid"
+    # rendering_network.sigma of a Fourier view embedder: the scale of its random matrix B ~ N(0, sigma^2) (embedder.py:128)
+    rgb_embed_sigma: float = 1.0
     # arithmetic of the MFMA kernels that have a bf16x3 twin (csrc/x3.h): fp32 operands split into three bf16 terms, six
     # partial products accumulated in fp32 -- fp32-level accuracy (same parity bar) on the 16x faster bf16 matrix pipe.
     # `bf16x3: false` in the model conf selects the plain fp32-MFMA kernels everywhere.
@@ -136,14 +149,42 @@ class NetConfig:
             raise NotImplementedError("rendering_network.embed_point: the reference builds that embedder and widens lin0 for it, but never "
                                       "applies it in forward() (model/network/mlp.py:185-190, 208-216: the raw points are concatenated), so the "
                                       "option cannot run there either")
-        mr_v = int(_get(rnet, "multires", 0)) if _get(rnet, "embed_type", None) else 0
+        # the view embedder (mlp.py:179-183 -> embedder.py:138-160): every other key of the node reaches the embedder's constructor
+        etype = _get(rnet, "embed_type", None)
+        embed, embed_n, sigma = "positional", 0, 1.0
+        if etype in ("spherical_harmonics", "fourier"):
+            if _has(rnet, "multires"):
+                raise NotImplementedError(f"rendering_network.multires beside embed_type {etype!r}: the reference hands it to that embedder's constructor, "
+                                          "which has no such argument (a TypeError there, mlp.py:181); remove the key")
+            if etype == "spherical_harmonics":
+                embed_n = int(_get(rnet, "degree", 4))         # (SHEncoder's default)
+                if not 1 <= embed_n <= 5:
+                    raise NotImplementedError(f"rendering_network.degree must be 1..5 (the reference's SHEncoder asserts it, embedder.py:50); got {embed_n}")
+            else:
+                if not _has(rnet, "channels"):
+                    raise NotImplementedError("rendering_network.embed_type 'fourier' needs `channels` (FourierFeature has no default, embedder.py:126)")
+                embed_n = int(_get(rnet, "channels"))
+                if not 1 <= embed_n <= 12:
+                    raise NotImplementedError(f"rendering_network.channels must be 1..12: the embedding [v | sin | cos] is 2 c + 3 wide and the radiance "
+                                              f"net's side row has 27 view columns; got {embed_n}")
+                if not _get(rnet, "include_input", True):
+                    raise NotImplementedError("rendering_network.include_input: false (a Fourier embedding without the raw direction) is not supported")
+                sigma = float(_get(rnet, "sigma", 1.0))
+            embed = etype
+        elif etype not in (None, False, "", "positional"):
+            raise NotImplementedError(f"rendering_network.embed_type must be 'positional', 'spherical_harmonics' or 'fourier' (the reference's "
+                                      f"get_embedder, model/network/embedder.py:138-160, has no other entry); got {etype!r}")
+        mr_v = int(_get(rnet, "multires", 0)) if etype and embed == "positional" else 0
         rhid = list(_get(rnet, "dims"))
         r_d_in = int(_get(rnet, "d_in"))
         if mode == "idr" and r_d_in != 9:
             raise NotImplementedError(f"rendering_network.d_in must be 9 (points, view directions, normals) in 'idr' mode; got {r_d_in}")
         r_in = r_d_in + fvs + (6 * mr_v if mr_v else 0)
+        if embed != "positional":
+            r_in = r_d_in + fvs + (embed_n ** 2 if embed == "spherical_harmonics" else 2 * embed_n + 3) - 3
         rfull = [r_in] + rhid + [int(_get(rnet, "d_out"))]
-        rgb = MlpShape("rendering_network", [(rfull[l + 1], rfull[l]) for l in range(len(rfull) - 1)], rhid[0], 9 if mode == "idr" else 3, mr_v)
+        rgb = MlpShape("rendering_network", [(rfull[l + 1], rfull[l]) for l in range(len(rfull) - 1)], rhid[0], 9 if mode == "idr" else 3, mr_v,
+                       embed=embed, embed_n=embed_n)
         light = None
         if _has(conf, "light_network"):
             lhid = list(_get(_get(conf, "light_network"), "dims"))
@@ -163,7 +204,7 @@ class NetConfig:
                 "instantiation in csrc/mlp_*.hip and csrc/plan.cpp for another width")
         if len(set(rhid)) != 1:
             raise NotImplementedError("radiance hidden widths must be uniform")
-        if multires != 6 or (mr_v not in (0, 4)):
+        if multires != 6 or (embed == "positional" and mr_v not in (0, 4)):
             raise NotImplementedError(f"positional encodings are instantiated for multires 6 (SDF net) and 4 (view directions); got {multires} / {mr_v}")
         if sam.N_samples_eval > 128 or sam.N_samples > 128 or sam.N_samples_eval * sam.max_total_iters > 640 or sam.max_total_iters > 12 \
                 or sam.N_samples + sam.N_samples_extra + 2 > 256:
@@ -177,7 +218,7 @@ class NetConfig:
                          scene_bounding_sphere=float(_get(conf, "scene_bounding_sphere", 1.0)),
                          beta_init=float(_get(_get(dens, "params_init"), "beta")), beta_min=float(_get(dens, "beta_min", 1e-4)),
                          sdf_bias=float(_get(inet, "bias", 1.0)), use_normal=bool(_get(conf, "use_normal", False)),
-                         detach_light_feature=bool(_get(conf, "detach_light_feature", True)), rgb_mode=mode, rgb_act=act,
+                         detach_light_feature=bool(_get(conf, "detach_light_feature", True)), rgb_mode=mode, rgb_act=act, rgb_embed_sigma=sigma,
                          bf16x3=bool(_get(conf, "bf16x3", True)), wgrad_bf16x2=bool(_get(conf, "wgrad_bf16x2", True)),
                          sampler_bf16x2=bool(_get(conf, "sampler_bf16x2", True)), saves24=bool(_get(conf, "saves24", True)))
 

@@ -476,6 +476,105 @@ __device__ __forceinline__ void pe_full(float x, float y, float z, float (&full)
     }
   }
 }
+// ---------------------------------------------------------------------------------------------
+// the radiance net's other view embedders (embedder.py:41-135; include/i2sdf.h: I2SDF_RGB_EMBED_*), chosen at run time: ONE kernel
+// instantiation serves every degree and channel count.  (kind, n) and B are kernel arguments, so every branch and select on them is
+// wave uniform.  A value is placed by its COMPILE-TIME slot index under such a select, never through a run-time index into the row: that
+// would put the row in scratch (the sampler's forward measured 24x slower with register arrays there, see relu0 above).
+// ---------------------------------------------------------------------------------------------
+constexpr int VE_SH = 1, VE_FOURIER = 2;          // == I2SDF_RGB_EMBED_SH / _FOURIER (plan.h: rgb_embed)
+constexpr int VE_SLOTS = 32;                      // the view row: 27 columns used at most, padded as the positional row is
+constexpr int VE_MAXC = 12;                       // Fourier channels (I2SDF_RGB_EMBED_MAX_CHANNELS)
+struct ViewEmbed {
+  int kind, n;                                    // n: SH degree 1..5 / Fourier channel count 1..12
+  float B[3 * VE_MAXC];                           // Fourier: row r of B (3, n) at B[12 r ..], zero beyond n (plan.cpp: i2sdf_plan_set_view_embed)
+};
+__device__ __forceinline__ int view_embed_dim(const ViewEmbed& ve) { return ve.kind == VE_SH ? ve.n * ve.n : 2 * ve.n + 3; }
+
+// E(v) in slots [0, e), exact zeros in [e, 32): the slots behind the row are reduction columns of layer 0 (their weights are zero) AND
+// columns of the saved row, a weight-gradient operand -- cos(0) = 1 of an unused Fourier channel must not get there.
+//   SH       the polynomial forms and constants of SHEncoder.forward (embedder.py:86-120), term by term
+//   Fourier  [v | sin(2 pi v.B) | cos(2 pi v.B)]: t = v.B[:, ch] is the phase in revolutions, t - rint(t) its exact fractional part,
+//            and v_sin_f32 / v_cos_f32 take revolutions directly (as pe_full)
+__device__ __forceinline__ void view_embed_full(const ViewEmbed& ve, float x, float y, float z, float (&full)[VE_SLOTS]) {
+#pragma unroll
+  for (int i = 0; i < VE_SLOTS; ++i) full[i] = 0.f;
+  const int n = ve.n;
+  if (ve.kind == VE_SH) {
+    full[0] = 0.28209479177387814f;
+    if (n > 1) {
+      constexpr float C1 = 0.4886025119029199f;
+      full[1] = -C1 * y; full[2] = C1 * z; full[3] = -C1 * x;
+      if (n > 2) {
+        const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
+        full[4] = 1.0925484305920792f * xy;
+        full[5] = -1.0925484305920792f * yz;
+        full[6] = 0.31539156525252005f * (2.0f * zz - xx - yy);          // (not 3 zz - 1: the reference's form, off the unit sphere too)
+        full[7] = -1.0925484305920792f * xz;
+        full[8] = 0.5462742152960396f * (xx - yy);
+        if (n > 3) {
+          full[9] = -0.5900435899266435f * y * (3.f * xx - yy);
+          full[10] = 2.890611442640554f * xy * z;
+          full[11] = -0.4570457994644658f * y * (4.f * zz - xx - yy);
+          full[12] = 0.3731763325901154f * z * (2.f * zz - 3.f * xx - 3.f * yy);
+          full[13] = -0.4570457994644658f * x * (4.f * zz - xx - yy);
+          full[14] = 1.445305721320277f * z * (xx - yy);
+          full[15] = -0.5900435899266435f * x * (xx - 3.f * yy);
+          if (n > 4) {
+            full[16] = 2.5033429417967046f * xy * (xx - yy);
+            full[17] = -1.7701307697799304f * yz * (3.f * xx - yy);
+            full[18] = 0.9461746957575601f * xy * (7.f * zz - 1.f);
+            full[19] = -0.6690465435572892f * yz * (7.f * zz - 3.f);
+            full[20] = 0.10578554691520431f * (zz * (35.f * zz - 30.f) + 3.f);
+            full[21] = -0.6690465435572892f * xz * (7.f * zz - 3.f);
+            full[22] = 0.47308734787878004f * (xx - yy) * (7.f * zz - 1.f);
+            full[23] = -1.7701307697799304f * xz * (xx - 3.f * yy);
+            full[24] = 0.6258357354491761f * (xx * (xx - 3.f * yy) - yy * (3.f * xx - yy));
+          }
+        }
+      }
+    }
+  } else {
+    full[0] = x; full[1] = y; full[2] = z;
+    float sn[VE_MAXC], cs[VE_MAXC];
+#pragma unroll
+    for (int ch = 0; ch < VE_MAXC; ++ch) {
+      const float t = fmaf(z, ve.B[2 * VE_MAXC + ch], fmaf(y, ve.B[VE_MAXC + ch], x * ve.B[ch]));
+      const float ph = t - rintf(t);
+      sn[ch] = __builtin_amdgcn_sinf(ph);
+      cs[ch] = __builtin_amdgcn_cosf(ph);
+    }
+    // slot 3 + j: sin of channel j while j < n; cos of channel ch where n == j - ch (and ch < n, i.e. 2 ch < j: known at compile time)
+#pragma unroll
+    for (int j = 0; j < 2 * VE_MAXC; ++j) {
+      float v = 0.f;
+      if (j < VE_MAXC) v = j < n ? sn[j] : 0.f;
+#pragma unroll
+      for (int ch = 0; ch < VE_MAXC; ++ch)
+        if (2 * ch < j && j - ch <= VE_MAXC) v = (n == j - ch) ? cs[ch] : v;
+      full[3 + j] = v;
+    }
+  }
+}
+// 'idr' mode: [x | E(v) | normal | 0 ...] in NS slots, the normal at the run-time offset 3 + e
+template <int NS>
+__device__ __forceinline__ void side_embed_idr(const ViewEmbed& ve, const float (&x)[3], float vx, float vy, float vz, const float (&nrm)[3],
+                                               float (&full)[NS]) {
+  static_assert(NS >= 3 + 27 + 3, "room for the widest row");
+  float ev[VE_SLOTS];
+  view_embed_full(ve, vx, vy, vz, ev);
+  const int e = view_embed_dim(ve);
+#pragma unroll
+  for (int i = 0; i < NS; ++i) full[i] = 0.f;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) full[j] = x[j];
+#pragma unroll
+  for (int i = 0; i < 30; ++i) {                    // slot 3 + i: E(v)[i] (zero from e on), or normal[i - e]
+    const float v = i < 27 ? ev[i] : 0.f;
+    full[3 + i] = (i == e) ? nrm[0] : (i == e + 1) ? nrm[1] : (i == e + 2) ? nrm[2] : v;
+  }
+}
+
 template <int NC>
 __device__ __forceinline__ void to_b_layout(const float (&full)[NC * 8], float (&regs)[NC * 4], int hi) {
 #pragma unroll

@@ -1,5 +1,6 @@
 // Argument blocks of the SDF training kernels (shared by the fp32 MFMA kernels and their bf16x3 twins in mlp_x3.hip).
 #pragma once
+#include <type_traits>
 #include "mlp_common.h"
 
 struct SdfTrainFwdArgs {
@@ -56,6 +57,12 @@ struct RgbFwdArgs {
   int act = 0;                          // output activation I2SDF_RGB_ACT_* (mlp_common.h: rgb_out_act), wave uniform
 };
 
+// the radiance forward with an SH / Fourier view embedder (common.h: view_embed_full): the same arguments and, by value, the embedder --
+// a type of its own, so that the kernels of the positional encoding keep their argument block
+struct RgbEmbedFwdArgs : RgbFwdArgs {
+  i2sdf::ViewEmbed ve;
+};
+
 struct RgbBwdArgs {
   const float* rev; int n_rev; int L;
   int64_t M, Mp;
@@ -82,6 +89,7 @@ void i2sdf_launch_rgb_fwd3h(const RgbFwdArgs& a, unsigned grid, hipStream_t st);
 void i2sdf_launch_rgb_bwd3h(const RgbBwdArgs& a, unsigned grid, hipStream_t st);
 void i2sdf_launch_rgb_fwd3h_idr(const RgbFwdArgs& a, int view_multires, unsigned grid, hipStream_t st);      // 4 or 0
 void i2sdf_launch_rgb_bwd3h_idr(const RgbBwdArgs& a, unsigned grid, hipStream_t st);
+void i2sdf_launch_rgb_fwd3h_embed(const RgbEmbedFwdArgs& a, bool idr, unsigned grid, hipStream_t st);
 // light-mask head forward on 16-point waves (mlp_x3h.hip): lm = sigmoid(W1 softplus100(W0 relu(feature) + b0) + b1), hl = the softplus activations
 struct LightFwd3hArgs {
   const float* fwd; int n_fwd;

@@ -240,8 +240,11 @@ __global__ __launch_bounds__(256) void sdf_train_fwd_split_kernel(SdfTrainFwdArg
 namespace {
 
 // IDR: the side row in front of the features is [x | PE(view) | normal] (33 of 40 columns) instead of PE(view) (27 of 32)
-template <int H, int F, int LFV, bool IDR = false>
-__global__ __launch_bounds__(256) void rgb_fwd_kernel(RgbFwdArgs a) {
+// Args = RgbEmbedFwdArgs: E(view) of the run-time SH / Fourier embedder in the place of PE(view), in the shapes of LFV = 4
+template <int H, int F, int LFV, bool IDR = false, class Args = RgbFwdArgs>
+__global__ __launch_bounds__(256) void rgb_fwd_kernel(Args a) {
+  constexpr bool EMB = std::is_same<Args, RgbEmbedFwdArgs>::value;
+  static_assert(!EMB || LFV == 4, "the run-time embedders fill the row of the positional encoding");
   constexpr int NT = H / 32, KC = H / 8, PECV = IDR ? cdiv(PE<LFV>::DIM + 6, 8) : PE<LFV>::PEC, FC = F / 8;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hi = lane >> 5;
@@ -252,7 +255,15 @@ __global__ __launch_bounds__(256) void rgb_fwd_kernel(RgbFwdArgs a) {
   float in0[(PECV + FC) * 4];
   {
     float full[PECV * 8], pv[PECV * 4];
-    if constexpr (IDR) {
+    if constexpr (EMB && IDR) {
+      float x[3], nrm[3];
+      fetch_point(a.pts, mc, x[0], x[1], x[2]);
+#pragma unroll
+      for (int j = 0; j < 3; ++j) nrm[j] = a.normals[mc * 3 + j];
+      side_embed_idr<PECV * 8>(a.ve, x, a.dirs[ray * 3 + 0], a.dirs[ray * 3 + 1], a.dirs[ray * 3 + 2], nrm, full);
+    } else if constexpr (EMB) {
+      view_embed_full(a.ve, a.dirs[ray * 3 + 0], a.dirs[ray * 3 + 1], a.dirs[ray * 3 + 2], full);
+    } else if constexpr (IDR) {
       constexpr int PD = PE<LFV>::DIM;
       float pe[PE<LFV>::PEC * 8];
       pe_full<LFV>(a.dirs[ray * 3 + 0], a.dirs[ray * 3 + 1], a.dirs[ray * 3 + 2], pe);
@@ -297,8 +308,10 @@ __global__ __launch_bounds__(256) void rgb_fwd_kernel(RgbFwdArgs a) {
 }
 
 // Split-K variant for the last partial round (ksplit.h): one 32-point tile per workgroup, points m0 + 32*blockIdx.x ...
-template <int H, int F, int LFV>
-__global__ __launch_bounds__(256) void rgb_fwd_split_kernel(RgbFwdArgs a, int64_t m0) {
+template <int H, int F, int LFV, class Args = RgbFwdArgs>
+__global__ __launch_bounds__(256) void rgb_fwd_split_kernel(Args a, int64_t m0) {
+  constexpr bool EMB = std::is_same<Args, RgbEmbedFwdArgs>::value;
+  static_assert(!EMB || LFV == 4, "the run-time embedders fill the row of the positional encoding");
   constexpr int NT = H / 32, KC = H / 8, PECV = PE<LFV>::PEC, FC = F / 8;
   static_assert(NT == 8 && KC == SC && FC == SC, "split-K kernels are built for 256-wide layers");
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -312,7 +325,8 @@ __global__ __launch_bounds__(256) void rgb_fwd_split_kernel(RgbFwdArgs a, int64_
   float in0[(PECV + FC) * 4];
   {
     float full[PECV * 8], pv[PECV * 4];
-    pe_full<LFV>(a.dirs[ray * 3 + 0], a.dirs[ray * 3 + 1], a.dirs[ray * 3 + 2], full);
+    if constexpr (EMB) view_embed_full(a.ve, a.dirs[ray * 3 + 0], a.dirs[ray * 3 + 1], a.dirs[ray * 3 + 2], full);
+    else pe_full<LFV>(a.dirs[ray * 3 + 0], a.dirs[ray * 3 + 1], a.dirs[ray * 3 + 2], full);
     to_b_layout<PECV>(full, pv, hi);
     if (a.pev_save && w == 0) store_regs<PECV>(a.pev_save + m * (PECV * 8), hi, valid, pv);
     float ft[FC * 4];
@@ -349,6 +363,15 @@ __global__ __launch_bounds__(256) void rgb_fwd_split_kernel(RgbFwdArgs a, int64_
 #pragma unroll
     for (int i = 0; i < 3; ++i) a.rgb[m * 3 + i] = rgb_out_act(a.act, o[i]);
   }
+}
+
+// the arguments of a radiance forward launch with the plan's run-time view embedder beside them (mlp_args.h)
+RgbEmbedFwdArgs with_view_embed(const i2sdf_plan* p, const RgbFwdArgs& a) {
+  RgbEmbedFwdArgs x{};
+  static_cast<RgbFwdArgs&>(x) = a;
+  x.ve.kind = rgb_embed(p->rgb.d); x.ve.n = p->rgb.d.multires;
+  for (int i = 0; i < 3 * VE_MAXC; ++i) x.ve.B[i] = p->view_B[i];
+  return x;
 }
 
 }  // namespace
@@ -428,7 +451,10 @@ extern "C" int i2sdf_rgb_forward(const i2sdf_plan* p, const float* packed, const
   if (!p || !packed || !dirs || !feat || !rgb || M < 0 || n_per_ray <= 0) return I2SDF_EINVAL;
   if (Mp < M || Mp % PTS_PER_WG) return I2SDF_EINVAL;
   const i2sdf_mlp_desc& d = p->rgb.d;
-  if (d.multires != 4 || rgb_idr(d)) return I2SDF_EINVAL;          // ('idr' plans: i2sdf_rgb_forward_idr)
+  const int emb = rgb_embed(d);                // the run-time SH / Fourier view embedders (include/i2sdf.h: I2SDF_RGB_EMBED_*)
+  if ((emb == I2SDF_RGB_EMBED_POSITIONAL && d.multires != 4) || rgb_idr(d)) return I2SDF_EINVAL;          // ('idr' plans: i2sdf_rgb_forward_idr)
+  if (emb == I2SDF_RGB_EMBED_FOURIER && !p->view_B_set)
+    return i2sdf_refuse("i2sdf_rgb_forward: the plan's Fourier view embedder has no matrix B yet (i2sdf_plan_set_view_embed)");
   const bool wide = d.hidden == 256 && p->F == 256, x3 = wide && p->rgb_bf16x3;
   if (!wide && !(d.hidden == 64 && p->F == 64)) return I2SDF_EINVAL;
   const Span fwd = span(p, packed, p->rgb, SPAN_FWD);
@@ -451,13 +477,20 @@ extern "C" int i2sdf_rgb_forward(const i2sdf_plan* p, const float* packed, const
   auto full = [&](hipStream_t s, int wg0, unsigned g, int64_t Mv) {
     RgbFwdArgs x = x3 ? a3 : a;
     x.wg0 = wg0; x.M = Mv;
-    if (x3) i2sdf_launch_rgb_fwd3h(x, g, s);
+    if (emb) {
+      const RgbEmbedFwdArgs xe = with_view_embed(p, x);
+      if (x3) i2sdf_launch_rgb_fwd3h_embed(xe, false, g, s);
+      else launch_lds(rgb_fwd_kernel<256, 256, 4, false, RgbEmbedFwdArgs>, g, s, xe);
+    } else if (x3) i2sdf_launch_rgb_fwd3h(x, g, s);
     else launch_lds(rgb_fwd_kernel<256, 256, 4>, g, s, x);
   };
   auto tail = [&](hipStream_t s, int64_t m0) {
-    launch_lds_bytes(KS_LDS_BYTES, rgb_fwd_split_kernel<256, 256, 4>, (unsigned)((M - m0 + 31) / 32), s, a, m0);
+    const unsigned g = (unsigned)((M - m0 + 31) / 32);
+    if (emb) launch_lds_bytes(KS_LDS_BYTES, rgb_fwd_split_kernel<256, 256, 4, RgbEmbedFwdArgs>, g, s, with_view_embed(p, a), m0);
+    else launch_lds_bytes(KS_LDS_BYTES, rgb_fwd_split_kernel<256, 256, 4>, g, s, a, m0);
   };
   if (wide) i2sdf_dispatch_points(p, st, M, ranged, true, TAIL_BEHIND, full, tail);
+  else if (emb) launch_lds(rgb_fwd_kernel<64, 64, 4, false, RgbEmbedFwdArgs>, (unsigned)((M + PTS_PER_WG - 1) / PTS_PER_WG), st, with_view_embed(p, a));
   else launch_lds(rgb_fwd_kernel<64, 64, 4>, (unsigned)((M + PTS_PER_WG - 1) / PTS_PER_WG), st, a);
   return i2sdf_hip_check(hipGetLastError(), "rgb_forward launch");
 }
@@ -472,7 +505,10 @@ extern "C" int i2sdf_rgb_forward_idr(const i2sdf_plan* p, const float* packed, c
   if (!points && (!cam || !z || ldz < n_per_ray)) return I2SDF_EINVAL;
   if (Mp < M || Mp % PTS_PER_WG) return I2SDF_EINVAL;
   const i2sdf_mlp_desc& d = p->rgb.d;
-  if ((d.multires != 4 && d.multires != 0) || !rgb_idr(d)) return I2SDF_EINVAL;
+  const int emb = rgb_embed(d);                // the run-time SH / Fourier view embedders (include/i2sdf.h: I2SDF_RGB_EMBED_*)
+  if ((emb == I2SDF_RGB_EMBED_POSITIONAL && d.multires != 4 && d.multires != 0) || !rgb_idr(d)) return I2SDF_EINVAL;
+  if (emb == I2SDF_RGB_EMBED_FOURIER && !p->view_B_set)
+    return i2sdf_refuse("i2sdf_rgb_forward_idr: the plan's Fourier view embedder has no matrix B yet (i2sdf_plan_set_view_embed)");
   const bool enc = d.multires == 4;               // view directions through PE4, or as they are (embed_type: null)
   const bool wide = d.hidden == 256 && p->F == 256, x3 = wide && p->rgb_bf16x3;
   if (!wide && !(d.hidden == 64 && p->F == 64)) return I2SDF_EINVAL;
@@ -491,7 +527,12 @@ extern "C" int i2sdf_rgb_forward_idr(const i2sdf_plan* p, const float* packed, c
   auto full = [&](hipStream_t s, int wg0, unsigned g, int64_t Mv) {
     RgbFwdArgs x = a;
     x.wg0 = wg0; x.M = Mv;
-    if (x3) i2sdf_launch_rgb_fwd3h_idr(x, enc ? 4 : 0, g, s);
+    if (emb) {
+      const RgbEmbedFwdArgs xe = with_view_embed(p, x);
+      if (x3) i2sdf_launch_rgb_fwd3h_embed(xe, true, g, s);
+      else if (wide) launch_lds(rgb_fwd_kernel<256, 256, 4, true, RgbEmbedFwdArgs>, g, s, xe);
+      else launch_lds(rgb_fwd_kernel<64, 64, 4, true, RgbEmbedFwdArgs>, g, s, xe);
+    } else if (x3) i2sdf_launch_rgb_fwd3h_idr(x, enc ? 4 : 0, g, s);
     else if (wide && enc) launch_lds(rgb_fwd_kernel<256, 256, 4, true>, g, s, x);
     else if (wide) launch_lds(rgb_fwd_kernel<256, 256, 0, true>, g, s, x);
     else if (enc) launch_lds(rgb_fwd_kernel<64, 64, 4, true>, g, s, x);

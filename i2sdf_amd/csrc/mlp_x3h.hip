@@ -145,8 +145,11 @@ __device__ __forceinline__ void side_select_h(const float (&x)[3], float vx, flo
 // radiance net (RenderingNetwork, mlp.py:208-229) forward and backward.  IDR: the side row in front of the features is [x | PE(view) | normal]
 // (two 32-chunks, saved 40 wide) instead of PE(view) (one 32-chunk, saved 32 wide); backward: two more tiles in the last reverse product, the
 // three normal rows of W_0^T in the first of them (plan.cpp: build_rgb) -> nbar
-template <int H, int F, int LFV, int NW, bool IDR = false>
-__global__ __launch_bounds__(NW * 64, 2) void rgb_fwd3h_kernel(RgbFwdArgs a) {
+// Args = RgbEmbedFwdArgs: E(view) of the run-time SH / Fourier embedder in the place of PE(view), in the shapes of LFV = 4
+template <int H, int F, int LFV, int NW, bool IDR = false, class Args = RgbFwdArgs>
+__global__ __launch_bounds__(NW * 64, 2) void rgb_fwd3h_kernel(Args a) {
+  constexpr bool EMB = std::is_same<Args, RgbEmbedFwdArgs>::value;
+  static_assert(!EMB || LFV == 4, "the run-time embedders fill the row of the positional encoding");
   constexpr int NT = H / 16, KH32 = H / 32, PECV = IDR ? cdiv(PE<LFV>::DIM + 6, 8) : PE<LFV>::PEC, PV32 = cdiv(PE<LFV>::DIM + (IDR ? 6 : 0), 32);
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, kg = lane >> 4;
@@ -155,7 +158,18 @@ __global__ __launch_bounds__(NW * 64, 2) void rgb_fwd3h_kernel(RgbFwdArgs a) {
   const int64_t mc = valid ? m : a.M - 1;
   const int64_t ray = mc / a.n_per_ray;
   float pev[PV32 * 8];
-  if constexpr (IDR) {
+  if constexpr (EMB && IDR) {
+    float x[3], n[3], pad[PV32 * 32];
+    fetch_point(a.pts, mc, x[0], x[1], x[2]);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) n[j] = a.normals[mc * 3 + j];
+    side_embed_idr<PV32 * 32>(a.ve, x, a.dirs[ray * 3 + 0], a.dirs[ray * 3 + 1], a.dirs[ray * 3 + 2], n, pad);
+    x3h_select<PV32>(pad, pev, kg);
+  } else if constexpr (EMB) {
+    float pad[PV32 * 32];
+    view_embed_full(a.ve, a.dirs[ray * 3 + 0], a.dirs[ray * 3 + 1], a.dirs[ray * 3 + 2], pad);
+    x3h_select<PV32>(pad, pev, kg);
+  } else if constexpr (IDR) {
     float x[3], n[3];
     fetch_point(a.pts, mc, x[0], x[1], x[2]);
 #pragma unroll
@@ -332,5 +346,9 @@ void i2sdf_launch_rgb_bwd3h(const RgbBwdArgs& a, unsigned grid, hipStream_t st) 
 void i2sdf_launch_rgb_fwd3h_idr(const RgbFwdArgs& a, int view_multires, unsigned grid, hipStream_t st) {
   if (view_multires == 4) launch_lds_threads(512, rgb_fwd3h_kernel<256, 256, 4, 8, true>, grid, st, a);
   else launch_lds_threads(512, rgb_fwd3h_kernel<256, 256, 0, 8, true>, grid, st, a);
+}
+void i2sdf_launch_rgb_fwd3h_embed(const RgbEmbedFwdArgs& a, bool idr, unsigned grid, hipStream_t st) {
+  if (idr) launch_lds_threads(512, rgb_fwd3h_kernel<256, 256, 4, 8, true, RgbEmbedFwdArgs>, grid, st, a);
+  else launch_lds_threads(512, rgb_fwd3h_kernel<256, 256, 4, 8, false, RgbEmbedFwdArgs>, grid, st, a);
 }
 void i2sdf_launch_rgb_bwd3h_idr(const RgbBwdArgs& a, unsigned grid, hipStream_t st) { launch_lds_threads(512, rgb_bwd3h_kernel<256, 256, 8, true>, grid, st, a); }

@@ -16,6 +16,11 @@ int i2sdf_hip_check(hipError_t e, const char* what) {
   return I2SDF_EHIP;
 }
 
+int i2sdf_refuse(const char* why) {
+  g_hip_err = why;
+  return I2SDF_EINVAL;
+}
+
 extern "C" int i2sdf_version(void) { return I2SDF_VERSION; }
 extern "C" const char* i2sdf_last_hip_error(void) { return g_hip_err.c_str(); }
 extern "C" const char* i2sdf_strerror(int code) {
@@ -58,7 +63,7 @@ Seg base_seg(const NetPlan& np, int l, int type) {
 }
 
 int pe_dim(const i2sdf_mlp_desc& d) { return side_dim(d); }      // (plan.h: one definition for every caller)
-int pe_chunks(const i2sdf_mlp_desc& d) { return cdiv(pe_dim(d), 8); }
+int pe_chunks(const i2sdf_mlp_desc& d) { return side_chunks(d); }
 
 ColMap cols(int n) { return ColMap{HUGE_SPLIT, 0, n, 0, 0}; }      // the first n columns, no split
 
@@ -226,10 +231,10 @@ int build_rgb(i2sdf_plan* p, Builder& b) {
   NetPlan& np = p->rgb;
   const i2sdf_mlp_desc& d = np.d;
   const bool idr = rgb_idr(d);
-  const int L = d.n_lin, H = d.hidden, PED = pe_dim(d), PEC = cdiv(PED, 8), F = p->F;
+  const int L = d.n_lin, H = d.hidden, PED = pe_dim(d), PEC = pe_chunks(d), F = p->F;
   if (check_mlp(d)) return I2SDF_EINVAL;
   if ((rgb_mode(d) != I2SDF_RGB_MODE_NERF && !idr) || (idr && d.d_in != 9)) return I2SDF_EINVAL;
-  if (rgb_act(d) > I2SDF_RGB_ACT_SOFTPLUS || (d.reserved & ~0xffff)) return I2SDF_EINVAL;      // (i2sdf_plan_create says why)
+  if (rgb_act(d) > I2SDF_RGB_ACT_SOFTPLUS || (d.reserved & 0xf0ff0000) || rgb_embed(d) > I2SDF_RGB_EMBED_FOURIER) return I2SDF_EINVAL;      // (i2sdf_plan_create says why)
   // the reverse product of layer 0: the feature rows of W_0^T; 'idr' adds one more tile behind them that holds the three normal rows
   const ColMap rev0 = idr ? ColMap{F, PED, F, PED - 3, 3} : ColMap{HUGE_SPLIT, PED, F, 0, 0};
   if (d.skip_layer >= 0 || d.d_out != 3 || (d.multires <= 0 && !idr) || d.in0 != PED + F || F <= 0) return I2SDF_EINVAL;
@@ -248,7 +253,7 @@ int build_rgb(i2sdf_plan* p, Builder& b) {
   // bf16x3 streams, 16-point-wave family (x3h.h): layer 0 reduces over [PE(view) padded to 32-chunks | feature]
   mark_here(np, b, {FWD3H, FWD3H_END, REV3H, REV3H_END});
   if (wide) {
-    const int PV32 = cdiv(PED, 32);
+    const int PV32 = cdiv(PEC * 8, 32);
     emit_dense(b, np, 0, X3H, H / 16, PV32 + F / 32, ColMap{PV32 * 32, 0, PED, PED, F}, 1.0f, 0, H);
     for (int l = 1; l < L - 1; ++l) emit_dense(b, np, l, X3H, H / 16, H / 32, cols(H), 1.0f, 0, H);
     emit_rowvec(b, np, L - 1, X3H, 3);
@@ -288,7 +293,7 @@ int build_light(i2sdf_plan* p, Builder& b) {
 // kind: 0 = sdf net, 1 = radiance net, 2 = light head
 void assign_scales_and_wgrad(i2sdf_plan* p, NetPlan& np, int kind) {
   const i2sdf_mlp_desc& d = np.d;
-  const int side = pe_dim(d), PEC8 = cdiv(side, 8) * 8;
+  const int side = pe_dim(d), PEC8 = pe_chunks(d) * 8;
   for (int l = 0; l < d.n_lin; ++l) {
     np.scale_off[l] = p->n_scale;
     p->n_scale += d.out_dim[l];
@@ -317,9 +322,49 @@ void assign_scales_and_wgrad(i2sdf_plan* p, NetPlan& np, int kind) {
 extern "C" int i2sdf_plan_create(const i2sdf_net_desc* desc, i2sdf_plan** out) {
   if (!desc || !out) return I2SDF_EINVAL;
   {  // shapes the kernels are instantiated for: refuse anything else here, with the reason (i2sdf_last_hip_error), not at the first launch
-    const int H = desc->sdf.hidden, Hr = desc->rgb.hidden, F = desc->rgb.n_lin > 0 ? desc->rgb.in0 - (rgb_idr(desc->rgb) ? side_dim(desc->rgb) : (desc->rgb.multires > 0 ? 3 + 6 * desc->rgb.multires : 3)) : 0;
+    // (bits 16..23 of rgb.reserved first: the message of the output activation's check covers them)
+    if (rgb_act(desc->rgb) > I2SDF_RGB_ACT_SOFTPLUS || (desc->rgb.reserved & 0x00ff0000)) {
+      g_hip_err = "i2sdf_plan_create: rgb.reserved " + std::to_string(desc->rgb.reserved) + ": output activation " + std::to_string(rgb_act(desc->rgb)) +
+                  " of the radiance net is not one of I2SDF_RGB_ACT_SIGMOID (0), I2SDF_RGB_ACT_RELU (1), I2SDF_RGB_ACT_SOFTPLUS (2) in bits 8..15"
+                  " (bits 16..23 must be zero)";
+      return I2SDF_EINVAL;
+    }
+    const int emb = rgb_embed(desc->rgb), n_emb = desc->rgb.multires;
+    if (emb > I2SDF_RGB_EMBED_FOURIER || (desc->rgb.reserved & 0xf0000000)) {
+      g_hip_err = "i2sdf_plan_create: rgb.reserved " + std::to_string(desc->rgb.reserved) + ": view embedder " + std::to_string(emb) +
+                  " of the radiance net is not one of I2SDF_RGB_EMBED_POSITIONAL (0), I2SDF_RGB_EMBED_SH (1), I2SDF_RGB_EMBED_FOURIER (2) in bits 24..27"
+                  " (bits 28..31 must be zero)";
+      return I2SDF_EINVAL;
+    }
+    if (emb == I2SDF_RGB_EMBED_SH && (n_emb < 1 || n_emb > 5)) {
+      g_hip_err = "i2sdf_plan_create: spherical-harmonics view embedder of degree " + std::to_string(n_emb) +
+                  " (rgb.multires): the reference's SHEncoder and the kernels have degrees 1..5";
+      return I2SDF_EINVAL;
+    }
+    if (emb == I2SDF_RGB_EMBED_FOURIER && (n_emb < 1 || n_emb > I2SDF_RGB_EMBED_MAX_CHANNELS)) {
+      g_hip_err = "i2sdf_plan_create: Fourier view embedder with " + std::to_string(n_emb) + " channels (rgb.multires): 1..12 fit the 27 view "
+                  "columns of the radiance net's side row (width 2 c + 3); more need wider rows";
+      return I2SDF_EINVAL;
+    }
+    const int H = desc->sdf.hidden, Hr = desc->rgb.hidden;
+    int F = 0;
+    if (desc->rgb.n_lin > 0) {
+      if (emb != I2SDF_RGB_EMBED_POSITIONAL) {
+        // the feature size cannot be derived from in0 here (that would accept any in0): the SDF net's output says it
+        F = desc->sdf.d_out - 1;
+        if (desc->rgb.in0 != side_dim(desc->rgb) + F) {
+          g_hip_err = "i2sdf_plan_create: rgb.in0 " + std::to_string(desc->rgb.in0) + " disagrees with the view embedder: " +
+                      (emb == I2SDF_RGB_EMBED_SH ? "spherical harmonics of degree " : "Fourier features with channels ") + std::to_string(n_emb) +
+                      " are " + std::to_string(embed_dim(desc->rgb)) + " wide, the side row " + std::to_string(side_dim(desc->rgb)) +
+                      ", so lin0 has " + std::to_string(side_dim(desc->rgb) + F) + " columns with feature size " + std::to_string(F);
+          return I2SDF_EINVAL;
+        }
+      } else {
+        F = desc->rgb.in0 - (rgb_idr(desc->rgb) ? side_dim(desc->rgb) : (desc->rgb.multires > 0 ? 3 + 6 * desc->rgb.multires : 3));
+      }
+    }
     const bool ok = (H == 256 && Hr == 256 && F == 256) || (H == 64 && Hr == 64 && F == 64);
-    if (!ok || desc->sdf.multires != 6 || (desc->rgb.multires != 4 && desc->rgb.multires != 0)) {
+    if (!ok || desc->sdf.multires != 6 || (emb == I2SDF_RGB_EMBED_POSITIONAL && desc->rgb.multires != 4 && desc->rgb.multires != 0)) {
       g_hip_err = "i2sdf_plan_create: SDF width " + std::to_string(H) + " / radiance width " + std::to_string(Hr) + " / feature size " + std::to_string(F) +
                   " / multires " + std::to_string(desc->sdf.multires) + "," + std::to_string(desc->rgb.multires) +
                   ": the MLP kernels are instantiated for 256/256/256 and 64/64/64 with multires 6 (points) and 4 (view directions) only";
@@ -327,12 +372,6 @@ extern "C" int i2sdf_plan_create(const i2sdf_net_desc* desc, i2sdf_plan** out) {
     }
     if (rgb_idr(desc->rgb) && desc->rgb.d_in != 9) {
       g_hip_err = "i2sdf_plan_create: the radiance net's 'idr' mode needs d_in 9 (points, view directions, normals)";
-      return I2SDF_EINVAL;
-    }
-    if (rgb_act(desc->rgb) > I2SDF_RGB_ACT_SOFTPLUS || (desc->rgb.reserved & ~0xffff)) {
-      g_hip_err = "i2sdf_plan_create: rgb.reserved " + std::to_string(desc->rgb.reserved) + ": output activation " + std::to_string(rgb_act(desc->rgb)) +
-                  " of the radiance net is not one of I2SDF_RGB_ACT_SIGMOID (0), I2SDF_RGB_ACT_RELU (1), I2SDF_RGB_ACT_SOFTPLUS (2) in bits 8..15"
-                  " (bits 16 and up must be zero)";
       return I2SDF_EINVAL;
     }
   }
@@ -576,6 +615,21 @@ extern "C" int i2sdf_plan_set_option(i2sdf_plan* p, int32_t option, int32_t valu
     return I2SDF_OK;
   }
   return I2SDF_EINVAL;
+}
+
+extern "C" int i2sdf_plan_set_view_embed(i2sdf_plan* p, const float* B_host, int32_t rows, int32_t cols) {
+  if (!p) return I2SDF_EINVAL;
+  const auto refuse = [](const std::string& why) { g_hip_err = "i2sdf_plan_set_view_embed: " + why; return I2SDF_EINVAL; };
+  if (rgb_embed(p->rgb.d) != I2SDF_RGB_EMBED_FOURIER) return refuse("the plan's radiance net has no Fourier view embedder (rgb.reserved bits 24..27)");
+  if (!B_host) return refuse("B_host is NULL");
+  if (rows != 3 || cols != p->rgb.d.multires)
+    return refuse("B is (" + std::to_string(rows) + ", " + std::to_string(cols) + "), the plan's embedder takes (3, " + std::to_string(p->rgb.d.multires) + ")");
+  for (int i = 0; i < 3 * cols; ++i)
+    if (!(B_host[i] - B_host[i] == 0.0f)) return refuse("B[" + std::to_string(i / cols) + "][" + std::to_string(i % cols) + "] is not finite");
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < I2SDF_RGB_EMBED_MAX_CHANNELS; ++c) p->view_B[r * I2SDF_RGB_EMBED_MAX_CHANNELS + c] = c < cols ? B_host[r * cols + c] : 0.0f;
+  p->view_B_set = 1;
+  return I2SDF_OK;
 }
 
 extern "C" int i2sdf_plan_set_exchange(i2sdf_plan* p, const i2sdf_exchange* ex, int32_t flags) {

@@ -71,13 +71,24 @@ constexpr SpanId SPAN_FWD2H{FWD2H, FWD2H_END, SCH};
 // [x | PE(view) | normal] (include/i2sdf.h: I2SDF_RGB_MODE_*), one contiguous block of lin0.weight_v in either mode
 // side_dim: THE width of a net's encoded input in front of the hidden / feature columns of its layer 0 -- PE(x) of the SDF net, the side row
 // of the radiance net, d_in of a net without encoding (plan.cpp, wgrad.hip and the launch sites all take it from here)
-// reserved = mode | act << 8 (include/i2sdf.h): the mode in bits 0..7, the output activation I2SDF_RGB_ACT_* in bits 8..15
+// reserved = mode | act << 8 | embed << 24 (include/i2sdf.h): the mode in bits 0..7, the output activation I2SDF_RGB_ACT_* in bits 8..15, the view
+// embedder I2SDF_RGB_EMBED_* in bits 24..27 (multires then carries the SH degree / the Fourier channel count)
 inline int rgb_mode(const i2sdf_mlp_desc& d) { return d.reserved & 0xff; }
 inline int rgb_act(const i2sdf_mlp_desc& d) { return (d.reserved >> 8) & 0xff; }
+inline int rgb_embed(const i2sdf_mlp_desc& d) { return (d.reserved >> 24) & 0xf; }
 inline bool rgb_idr(const i2sdf_mlp_desc& d) { return rgb_mode(d) == I2SDF_RGB_MODE_IDR; }
+// width e of the embedded view direction E(v) of a radiance net with an SH / Fourier embedder
+inline int embed_dim(const i2sdf_mlp_desc& d) { return rgb_embed(d) == I2SDF_RGB_EMBED_SH ? d.multires * d.multires : 2 * d.multires + 3; }
 inline int side_dim(const i2sdf_mlp_desc& d) {
+  if (rgb_embed(d) != I2SDF_RGB_EMBED_POSITIONAL) return embed_dim(d) + (rgb_idr(d) ? 6 : 0);      // [E(v)] / [x | E(v) | normal]
   const int raw = rgb_idr(d) ? 3 : d.d_in;          // 'idr': only the view direction (3 of the 9 raw inputs) is encoded
   return (d.multires > 0 ? raw + 2 * raw * d.multires : raw) + (rgb_idr(d) ? 6 : 0);
+}
+// 8-column chunks the side row occupies in the padded spaces (fp32 streams, saved row, weight-gradient block).  An SH / Fourier row keeps
+// the positional row's 32 ('nerf') / 40 ('idr') columns whatever its own width: one kernel instantiation and one set of shapes for all of them
+inline int side_chunks(const i2sdf_mlp_desc& d) {
+  if (rgb_embed(d) != I2SDF_RGB_EMBED_POSITIONAL) return rgb_idr(d) ? 5 : 4;
+  return (side_dim(d) + 7) / 8;
 }
 
 struct NetPlan {
@@ -122,8 +133,15 @@ struct i2sdf_plan {
   mutable hipStream_t part_st[I2SDF_MAX_PARTS - 1] = {nullptr, nullptr, nullptr};
   mutable hipEvent_t part_ev[I2SDF_MAX_PARTS] = {nullptr, nullptr, nullptr, nullptr};   // [0] fork event, [q] join event of part q
   mutable int32_t chain_active = 0;          // between i2sdf_chain_begin and i2sdf_chain_end
+  // i2sdf_plan_set_view_embed: B of a Fourier view embedder, row r at view_B[12 r ..] (zero beyond the channel count), passed to the
+  // radiance forward kernels by value (mlp_args.h: RgbEmbedFwdArgs)
+  float view_B[3 * I2SDF_RGB_EMBED_MAX_CHANNELS] = {};
+  int32_t view_B_set = 0;
   mutable int64_t chain_M = 0;               // the point count the active chain's ranges were cut from
 };
+
+// An entry point's refusal with a reason: the text goes where i2sdf_last_hip_error() finds it; returns I2SDF_EINVAL (plan.cpp)
+int i2sdf_refuse(const char* why);
 
 // ---- spans of the weight streams ----------------------------------------------------------------------------------
 // What a kernel takes: where its weight stream starts and how many LDS stages it walks.  n_stages == 0: the span was refused -- empty

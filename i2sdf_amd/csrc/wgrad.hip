@@ -1071,7 +1071,7 @@ struct TaskList {
 void fill_wn(WnTab& tab, const NetPlan& np, int kind, int& row0) {
   const i2sdf_mlp_desc& d = np.d;
   const bool enc = d.multires > 0 || rgb_idr(d);        // a PE / side block in front of the hidden or feature columns (plan.h: side_dim)
-  const int PED = side_dim(d), PEC8 = enc ? cdiv(PED, 8) * 8 : 0;
+  const int PED = side_dim(d), PEC8 = enc ? side_chunks(d) * 8 : 0;
   for (int l = 0; l < d.n_lin; ++l) {
     WnLayer& y = tab.l[tab.n++];
     y.off_v = d.off_v[l]; y.off_g = d.off_g[l]; y.off_bias = d.off_bias[l];
@@ -1134,7 +1134,7 @@ extern "C" int i2sdf_weight_grads(const i2sdf_plan* p, const i2sdf_train_buffers
   if (Mm > 0 && tb->gar) {  // ---- radiance net
     const NetPlan& np = p->rgb;
     const i2sdf_mlp_desc& d = np.d;
-    const int L = d.n_lin, H = d.hidden, F = p->F, PV8 = cdiv(d.in0 - F, 8) * 8;
+    const int L = d.n_lin, H = d.hidden, F = p->F, PV8 = side_chunks(d) * 8;
     const int64_t ls = Mp * H;
     const int64_t br = (H == 256) ? rgb_blocked_points(p, Mm, Mp) : 0;     // leading points of rs / gar in the blocked layout
     for (int l = 0; l < L; ++l) {

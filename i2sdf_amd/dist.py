@@ -262,6 +262,12 @@ def broadcast_parameters(net, src: int = 0, group=None):
     else:
         for p in net.parameters():
             dist.broadcast(p.data, src=src, group=group)
+    # what the ranks drew on their own that is no parameter: the Fourier view embedder's matrix.  It is replicated once here and never
+    # reduced -- it has no gradient and is not part of the flat buffer the gradient mean runs over
+    for b in net.buffers():
+        dist.broadcast(b, src=src, group=group)
+    if hasattr(net, "sync_view_embed"):
+        net.sync_view_embed()
 
 
 def shard_range(total: int, rank: int, world: int) -> Tuple[int, int]:

@@ -383,15 +383,27 @@ class RenderEngine:
         rgb_forward / rgb_backward, render_image and both loss routes take it from there; `rgb` may exceed 1 with the last two"""
         return self.cfg.rgb_act
 
+    def set_view_embed(self, B: torch.Tensor):
+        """The matrix B (3, channels) of a Fourier view embedder (include/i2sdf.h: i2sdf_plan_set_view_embed): copied into the plan from
+        HOST memory; the radiance forward launches enqueued from now on carry it by value.  Once per engine and per loaded checkpoint."""
+        B = B.detach().to("cpu", torch.float32).contiguous()
+        if B.dim() != 2:
+            raise ValueError(f"set_view_embed: B must be (3, channels); got {tuple(B.shape)}")
+        L.check(self._lib.i2sdf_plan_set_view_embed(self._plan, C.c_void_p(B.data_ptr()), B.shape[0], B.shape[1]), "i2sdf_plan_set_view_embed")
+        self.view_embed_B = B
+
     def rgb_forward(self, dirs, n_per_ray, feat, M, save=True, fw=None, points=None, normals=None):
         """'idr' mode needs the points and normals of the M points: `fw`, the dict of the sdf_forward_grad call that produced `feat` (its
         leading M points are ray samples), or explicit `points` (M,3) and `normals` (M,3).  `pev` is the saved side row: (Mp,32) PE(view)
-        in 'nerf' mode, (Mp,40) [x | PE(view) | normal] in 'idr' mode ((Mp,16) with unencoded view directions)."""
+        in 'nerf' mode, (Mp,40) [x | PE(view) | normal] in 'idr' mode ((Mp,16) with unencoded view directions).  With a spherical-harmonics
+        or Fourier view embedder E(view) stands where PE(view) does and the row keeps its 32 / 40 columns, zero from its own width on."""
         Mp = feat.shape[0]
         rgb = torch.empty(M, 3, dtype=torch.float32, device=feat.device)
         Lr, Hr = self.cfg.rgb.n_lin, self.cfg.rgb.hidden
         rs = self._ws(Lr - 1, Mp, Hr, device=feat.device) if save else None
-        pev = self._ws(Mp, (self.cfg.rgb.pe_dim + 7) // 8 * 8 if self.idr else 32, device=feat.device) if save else None
+        side = (40 if self.idr else 32) if self.cfg.rgb.embed != "positional" else ((self.cfg.rgb.pe_dim + 7) // 8 * 8 if self.idr else 32)
+        pev = self._ws(Mp, side, device=feat.device) if save else None
+        no_B = self.cfg.rgb.embed == "fourier" and getattr(self, "view_embed_B", None) is None      # (the one refusal that leaves its reason)
         if self.idr:
             cam = z = pts = None
             ldz = 0
@@ -413,10 +425,10 @@ class RenderEngine:
                 raise ValueError(f"rgb_forward: {dirs.shape[0]} view directions x {n_per_ray} samples for {M} points")
             L.check(self._lib.i2sdf_rgb_forward_idr(self._plan, self._pk(), L.ptr(pts), L.ptr(cam), L.ptr(dirs), L.ptr(z), ldz, n_per_ray,
                                                     L.ptr(nrm), L.ptr(feat), M, Mp, L.ptr(rgb), L.ptr(rs), L.ptr(pev), L.stream_ptr()),
-                    "i2sdf_rgb_forward_idr")
+                    "i2sdf_rgb_forward_idr", reason=no_B)
             return rgb, rs, pev
         L.check(self._lib.i2sdf_rgb_forward(self._plan, self._pk(), L.ptr(dirs.contiguous()), n_per_ray, L.ptr(feat), M, Mp,
-                                             L.ptr(rgb), L.ptr(rs), L.ptr(pev), L.stream_ptr()), "i2sdf_rgb_forward")
+                                             L.ptr(rgb), L.ptr(rs), L.ptr(pev), L.stream_ptr()), "i2sdf_rgb_forward", reason=no_B)
         return rgb, rs, pev
 
     def rgb_backward(self, rgb, rgb_bar, rs, M, nbar=None, accumulate=True):

@@ -78,6 +78,8 @@ MAX_PARTS = 4
 GRID_ORDER_MESHGRID, GRID_ORDER_VOLUME = 0, 1
 RGB_MODE_NERF, RGB_MODE_IDR = 0, 1    # I2SDF_RGB_MODE_*: i2sdf_net_desc.rgb.reserved, bits 0..7
 RGB_ACTS = {"sigmoid": 0, "relu": 1, "softplus": 2}      # I2SDF_RGB_ACT_*: the same field, bits 8..15 (reserved = mode | act << 8)
+RGB_EMBEDS = {"positional": 0, "spherical_harmonics": 1, "fourier": 2}      # I2SDF_RGB_EMBED_*: the same field, bits 24..27
+RGB_EMBED_MAX_CHANNELS = 12      # I2SDF_RGB_EMBED_MAX_CHANNELS
 RASTER_SMALL_MAX = 64            # I2SDF_RASTER_SMALL_MAX
 TSDF_MAX_CELLS = 1 << 24         # I2SDF_TSDF_MAX_CELLS
 IMAGE_STATS = 8                  # I2SDF_IMAGE_STATS
@@ -111,6 +113,8 @@ SIGNATURES = {
     "i2sdf_sdf_forward": (C.c_int, [_P, _P, _P, _I64, _P, _P, _I64, _P]),
     # plan, packed, points, cam, dirs, z, ldz, n_per_ray, n_ray_pts, M, Mp, sdf, feat, grad, hs, abars, pe_save, stream
     "i2sdf_sdf_forward_grad": (C.c_int, [_P] * 6 + [_I64, _I32, _I64, _I64, _I64] + [_P] * 7),
+    # plan, B_host (3, c) fp32 in host memory, rows, cols
+    "i2sdf_plan_set_view_embed": (C.c_int, [_P, _P, _I32, _I32]),
     # plan, packed, dirs, n_per_ray, feat, M, Mp, rgb, rs, pev_save, stream
     "i2sdf_rgb_forward": (C.c_int, [_P, _P, _P, _I32, _P, _I64, _I64, _P, _P, _P, _P]),
     # plan, packed, rgb, rgb_bar, rs, M, Mp, gar, ga_last, fbar, stream
@@ -276,11 +280,13 @@ def load():
     return lib
 
 
-def check(rc: int, what: str = ""):
+def check(rc: int, what: str = "", reason: bool = False):
+    """reason: the entry point leaves the reason of an I2SDF_EINVAL where i2sdf_last_hip_error() finds it"""
     if rc != 0:
         lib = load()
         msg = lib.i2sdf_strerror(rc).decode()
-        if rc == -2 or (rc == -1 and what == "i2sdf_plan_create"):      # (plan creation leaves the reason of a refused shape there)
+        # (plan creation leaves the reason of a refused shape there; the view embedder's entry points the reason of their refusals)
+        if rc == -2 or (rc == -1 and (reason or what in ("i2sdf_plan_create", "i2sdf_plan_set_view_embed"))):
             msg += ": " + lib.i2sdf_last_hip_error().decode()
         if rc == -5:
             msg += ": " + lib.i2sdf_last_comm_error().decode()

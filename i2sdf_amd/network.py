@@ -33,13 +33,33 @@ class _WNLinear(nn.Module):
 class _Mlp(nn.Module):
     def __init__(self, shape: MlpShape):
         super().__init__()
+        self._before_layers(shape)
         self.shape = shape
         self.num_layers = shape.n_lin + 1
         for l, (out, inn) in enumerate(shape.dims):
             setattr(self, f"lin{l}", _WNLinear(out, inn))
 
+    def _before_layers(self, shape: MlpShape):
+        """sub-modules the reference registers in front of lin0 (their state_dict keys come first)"""
+
     def get_param_groups(self, lr):
         return [{"params": self.parameters(), "lr": lr}]
+
+
+class FourierFeature(nn.Module):
+    """model/network/embedder.py:125-135 as a container: the random matrix B (3, channels) is a persistent BUFFER -- in the state_dict
+    under the reference's key, loaded by load_state_dict, moved by .to(), but no parameter: not in parameters(), not in the flat parameter
+    buffer, never seen by an optimizer or a gradient all-reduce.  The kernels get it from the plan (include/i2sdf.h:
+    i2sdf_plan_set_view_embed); I2SDFNetwork hands it over when an engine is built and after load_state_dict -- after any other write
+    to it call I2SDFNetwork.sync_view_embed()."""
+
+    def __init__(self, channels: int, sigma: float = 1.0, input_dims: int = 3):
+        super().__init__()
+        # zeros until I2SDFNetwork._init_parameters draws it where the reference does: behind the SDF net's initialisation, in front of
+        # the radiance layers' (params.py: init_flat)
+        self.register_buffer("B", torch.zeros(input_dims, channels), True)
+        self.channels, self.sigma, self.include_input = channels, sigma, True
+        self.out_dim = 2 * channels + 3
 
 
 class ImplicitNetwork(_Mlp):
@@ -71,10 +91,16 @@ class ImplicitNetwork(_Mlp):
 
 
 class RenderingNetwork(_Mlp):
-    def __init__(self, shape: MlpShape, mode: str, output_activation: str = "sigmoid"):
+    def __init__(self, shape: MlpShape, mode: str, output_activation: str = "sigmoid", embed_sigma: float = 1.0):
+        self._embed_sigma = embed_sigma
         super().__init__(shape)
         self.mode = mode
         self.output_activation = output_activation      # 'sigmoid' | 'relu' | 'softplus' (no parameters: the state_dict does not change)
+
+    def _before_layers(self, shape: MlpShape):
+        # (mlp.py:179-183) the Fourier embedder is a sub-module with a buffer; spherical harmonics and the positional encoding have no state
+        sigma = self.__dict__.pop("_embed_sigma", 1.0)
+        self.embedview_fn = FourierFeature(shape.embed_n, sigma) if shape.embed == "fourier" else None
 
 
 class LaplaceDensity(nn.Module):
@@ -320,7 +346,7 @@ class I2SDFNetwork(nn.Module):
         self.feature_vector_size = cfg.feature_size
         self.scene_bounding_sphere = cfg.scene_bounding_sphere
         self.implicit_network = ImplicitNetwork(cfg.sdf, self)
-        self.rendering_network = RenderingNetwork(cfg.rgb, cfg.rgb_mode, cfg.rgb_act)
+        self.rendering_network = RenderingNetwork(cfg.rgb, cfg.rgb_mode, cfg.rgb_act, cfg.rgb_embed_sigma)
         self.use_light = cfg.light is not None
         if self.use_light:
             self.light_network = _Mlp(cfg.light)
@@ -342,6 +368,8 @@ class I2SDFNetwork(nn.Module):
         object.__setattr__(self, "_flat", None)
         object.__setattr__(self, "_packed", set())
         self._init_parameters()
+        # a loaded checkpoint brings its own Fourier matrix: the plans of the engines built so far must see it
+        self.register_load_state_dict_post_hook(lambda module, incompatible: module.sync_view_embed())
 
     # ------------------------------------------------------------------------------------------
     def _param_list(self):
@@ -349,13 +377,27 @@ class I2SDFNetwork(nn.Module):
         return [sd[name] for name, _, _ in self.layout.entries]
 
     def _init_parameters(self, generator=None):
-        flat = self.layout.init_flat(generator)
+        buffers = {}
+        flat = self.layout.init_flat(generator, buffers)
         with torch.no_grad():
+            for name, val in buffers.items():
+                self.get_buffer(name).copy_(val)
             for (name, off, shape), p in zip(self.layout.entries, self._param_list()):
                 p.copy_(flat[off:off + p.numel()].view(shape))
 
     def get_param_groups(self, lr):
         return [{"params": self.parameters(), "lr": lr}]
+
+    def sync_view_embed(self):
+        """Hand the Fourier view embedder's matrix B (rendering_network.embedview_fn.B) to the plan of every engine built so far.  Done
+        when an engine is built and after load_state_dict -- NOT per step: B is a constant of the net.  Call it after writing to the buffer
+        by any other way.  (One small device-to-host copy; nothing to do for the other embedders.)"""
+        ff = self.rendering_network.embedview_fn
+        if ff is None or not self._engines:
+            return
+        B = ff.B.detach().to("cpu", torch.float32).contiguous()
+        for eng in self._engines.values():
+            eng.set_view_embed(B)
 
     def _ensure_flat(self):
         """Keep every parameter a view into one flat fp32 buffer (the layout the C ABI and the gradient all-reduce use)."""
@@ -395,6 +437,7 @@ class I2SDFNetwork(nn.Module):
             with torch.inference_mode(False), torch.cuda.device(device):
                 eng = RenderEngine(self.cfg, device)
             self._engines[key] = eng
+            self.sync_view_embed()
         # The parameters are views of `flat` made through `.data`, so they keep their OWN version counters, and fused /
         # foreach optimizers or raw-pointer writers need not bump any of them: no version key can tell whether the packed
         # weight streams are stale.  Packing costs ~17 us, so every public entry point (fresh=True) simply repacks; only

@@ -8,7 +8,7 @@ import numpy as np
 import torch
 
 from .config import MlpShape, NetConfig
-from .lib import MAX_LAYERS, RGB_ACTS, RGB_MODE_IDR, RGB_MODE_NERF, MlpDesc, NetDesc
+from .lib import MAX_LAYERS, RGB_ACTS, RGB_EMBEDS, RGB_MODE_IDR, RGB_MODE_NERF, MlpDesc, NetDesc
 
 
 class ParamLayout:
@@ -54,7 +54,9 @@ class ParamLayout:
         nd = NetDesc()
         nd.sdf = self._mlp_desc(c.sdf, c.sdf.dims[-1][0])
         nd.rgb = self._mlp_desc(c.rgb, c.rgb.dims[-1][0])
-        nd.rgb.reserved = (RGB_MODE_IDR if c.rgb_mode == "idr" else RGB_MODE_NERF) | RGB_ACTS[c.rgb_act] << 8
+        nd.rgb.reserved = (RGB_MODE_IDR if c.rgb_mode == "idr" else RGB_MODE_NERF) | RGB_ACTS[c.rgb_act] << 8 | RGB_EMBEDS[c.rgb.embed] << 24
+        if c.rgb.embed != "positional":
+            nd.rgb.multires = c.rgb.embed_n          # (the SH degree / the Fourier channel count, include/i2sdf.h: I2SDF_RGB_EMBED_*)
         if c.light is not None:
             nd.light = self._mlp_desc(c.light, 1)
         nd.off_beta = self.offset("density.beta")
@@ -64,11 +66,13 @@ class ParamLayout:
         return nd
 
     # ------------------------------------------------------------------------------------------
-    def init_flat(self, generator: torch.Generator = None) -> torch.Tensor:
+    def init_flat(self, generator: torch.Generator = None, buffers: Dict[str, torch.Tensor] = None) -> torch.Tensor:
         """Reference initialisation scheme, written into a new flat CPU tensor.
         SDF net: geometric init (model/network/mlp.py:55-69); radiance / light nets: nn.Linear default
         (U(+-1/sqrt(in)) for weight and bias); weight_norm: v = W, g = row norms (mlp.py:71-72);
-        density.beta from the config (density.py:6-8)."""
+        density.beta from the config (density.py:6-8).  `buffers` (a dict) receives what the reference draws on the way that is no
+        parameter: the Fourier view embedder's B = randn(3, channels) * sigma (embedder.py:128), drawn where its constructor runs --
+        behind the SDF net, in front of the radiance layers (mlp.py:179-203)."""
         c = self.cfg
         flat = torch.zeros(self.n_params, dtype=torch.float32)
 
@@ -91,6 +95,8 @@ class ParamLayout:
                 elif l == c.sdf.skip_layer:
                     W[:, -(pe - 3):] = 0.0
             put(f"implicit_network.lin{l}", W, b)
+        if c.rgb.embed == "fourier" and buffers is not None:
+            buffers["rendering_network.embedview_fn.B"] = torch.randn(3, c.rgb.embed_n, generator=generator) * c.rgb_embed_sigma
         for net in self.nets()[1:]:
             for l, (out, inn) in enumerate(net.dims):
                 bound = 1.0 / math.sqrt(inn)

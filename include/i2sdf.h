@@ -48,9 +48,11 @@ typedef struct i2sdf_mlp_desc {
   int32_t d_in;                           /* raw input dims of layer 0 before encoding               */
   int32_t in0;                            /* columns of lin0.weight_v                                */
   int32_t d_out;                          /* rows of the last layer                                  */
-  int32_t multires;                       /* positional-encoding frequencies L (embedder.py:138-152) */
+  int32_t multires;                       /* positional-encoding frequencies L (embedder.py:138-152); radiance net with another view
+                                             embedder (I2SDF_RGB_EMBED_*): the SH degree or the Fourier channel count */
   int32_t skip_layer;                     /* l with `l in skip_in` (mlp.py:94), -1 if none           */
-  int32_t reserved;                       /* radiance net: I2SDF_RGB_MODE_* | I2SDF_RGB_ACT_* << 8 (0 = 'nerf', sigmoid); 0 for the other nets */
+  int32_t reserved;                       /* radiance net: I2SDF_RGB_MODE_* | I2SDF_RGB_ACT_* << 8 | I2SDF_RGB_EMBED_* << 24 (0 = 'nerf', sigmoid,
+                                             positional); 0 for the other nets */
   int32_t out_dim[I2SDF_MAX_LAYERS];      /* rows of weight_v per layer                              */
   int32_t in_dim[I2SDF_MAX_LAYERS];       /* cols of weight_v per layer                              */
   int64_t off_bias[I2SDF_MAX_LAYERS];
@@ -78,6 +80,23 @@ typedef struct i2sdf_mlp_desc {
 #define I2SDF_RGB_ACT_SIGMOID 0
 #define I2SDF_RGB_ACT_RELU 1
 #define I2SDF_RGB_ACT_SOFTPLUS 2
+/* rendering_network.embed_type (embedder.py:138-160), the embedder E of the unit view direction v, in bits 24..27 of the same field;
+ * rgb.multires carries its parameter.  e = the width of E(v); the side row is [E(v)] ('nerf', in0 = e + F) or [point | E(v) | normal]
+ * ('idr', in0 = e + 6 + F).  Bits 16..23 and 28..31 must be zero.
+ *   I2SDF_RGB_EMBED_POSITIONAL  multires = L in {4, 0}: [v | sin(2^k v), cos(2^k v), k < L], e = 3 + 6 L (L = 0: v itself).  A descriptor
+ *                               written before the other embedders existed (bits 24..27 zero) keeps its value and meaning.
+ *   I2SDF_RGB_EMBED_SH          multires = degree in 1..5: the real spherical harmonics below that degree in the polynomial forms and
+ *                               constants of SHEncoder (embedder.py:84-122), e = degree^2.  No state.
+ *   I2SDF_RGB_EMBED_FOURIER     multires = channels c in 1..12: [v | sin(2 pi v B) | cos(2 pi v B)] (FourierFeature, include_input), e = 2 c + 3.
+ *                               B (3, c) is a buffer of the module, not a parameter: i2sdf_plan_set_view_embed hands it to the plan.
+ * Every e up to 27 fits the columns the positional encoding already has (27 of 32 in 'nerf', 33 of 40 in 'idr' mode): the packed streams,
+ * the saved side row (pev_save: (Mp,32) / (Mp,40), columns at and beyond the row's width exactly zero) and the weight-gradient blocks keep
+ * the sizes of the positional plan.  i2sdf_plan_create refuses an unknown kind, a degree or channel count out of range and an in0 that
+ * disagrees with e, each with I2SDF_EINVAL and a text in i2sdf_last_hip_error(). */
+#define I2SDF_RGB_EMBED_POSITIONAL 0
+#define I2SDF_RGB_EMBED_SH 1
+#define I2SDF_RGB_EMBED_FOURIER 2
+#define I2SDF_RGB_EMBED_MAX_CHANNELS 12
 
 typedef struct i2sdf_net_desc {
   i2sdf_mlp_desc sdf;                     /* ImplicitNetwork: PE(x) -> softplus100 stack -> [sdf | feature]   */
@@ -232,10 +251,21 @@ int i2sdf_sdf_forward_grad(const i2sdf_plan* plan, const float* packed, const fl
                            void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The matrix B of a Fourier view embedder (I2SDF_RGB_EMBED_FOURIER): B_host (rows, cols) = (3, c) row-major fp32 in HOST memory, c the
+ * plan's rgb.multires.  The plan keeps a copy; the radiance forward entry points (i2sdf_rgb_forward, i2sdf_rgb_forward_idr and everything
+ * built on them: i2sdf_render_image) pass it to their kernels by value -- no device allocation, no copy, no synchronisation.  Call it once
+ * after i2sdf_plan_create and again whenever B changes (a loaded checkpoint); a call takes effect for the launches enqueued after it.
+ * I2SDF_EINVAL with a text in i2sdf_last_hip_error(): a plan of another embedder, rows != 3, cols != c, a NULL or non-finite B_host.
+ * On a Fourier plan a radiance forward BEFORE the first call returns I2SDF_EINVAL (text in i2sdf_last_hip_error()) and launches nothing.
+ * ---------------------------------------------------------------------------------------------- */
+int i2sdf_plan_set_view_embed(i2sdf_plan* plan, const float* B_host, int32_t rows, int32_t cols);
+
+/* ------------------------------------------------------------------------------------------------
  * Radiance network forward, 'nerf' mode -- RenderingNetwork.forward (mlp.py:208-229):
  * rgb = act(MLP([PE4(view_dir) | feature])), act = the plan's I2SDF_RGB_ACT_* (sigmoid unless the descriptor says otherwise).
  * dirs (B,3) unit view directions, point m uses dirs[m / n_per_ray].
  *   rgb (M,3) ; rs (L-1, Mp, H) post-ReLU activations and pev_save (Mp,32) PE(view) (NULL if no backward follows)
+ * With I2SDF_RGB_EMBED_SH / _FOURIER, E(view_dir) takes the place of PE4(view_dir) here and in 'idr' mode; pev_save keeps its width.
  * ---------------------------------------------------------------------------------------------- */
 int i2sdf_rgb_forward(const i2sdf_plan* plan, const float* packed, const float* dirs, int32_t n_per_ray, const float* feat,
                       int64_t M, int64_t Mp, float* rgb, float* rs, float* pev_save, void* stream);
