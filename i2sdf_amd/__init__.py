@@ -31,6 +31,9 @@ def __getattr__(name):
     if name in ("psnr", "ssim", "image_stats", "image_metrics", "to_frames", "interpolate_poses", "pixel_grid", "linear_to_srgb"):
         from . import views
         return getattr(views, name)
+    if name in ("RenderingLayer", "get_rendering_parameters", "shade_draws"):
+        from . import shading
+        return getattr(shading, name)
     if name == "RenderEngine":
         from .engine import RenderEngine
         return RenderEngine

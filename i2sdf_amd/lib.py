@@ -237,6 +237,16 @@ SIGNATURES = {
     "i2sdf_depth_unproject_count": (C.c_int, [_P, _I64, _I32, _I32, _F, _F, _P, _P, C.POINTER(_I64), _P]),
     # depth, intrinsics, pose, n_img, H, W, lo, hi, workspace, n_points, pointlinks, pixlinks, pointcloud, stream
     "i2sdf_depth_unproject_write": (C.c_int, [_P, _P, _P, _I64, _I32, _I32, _F, _F, _P, _I64, _P, _P, _P, _P]),
+    # seed, bn, spp, samples, stream
+    "i2sdf_shade_draws": (C.c_int, [C.c_uint64, _I64, _I32, _P, _P]),
+    # surface_points, view_direction, normal, Kd, Ks, rough, samples, seed (host), bn, spp, direction, points, wi_mask, stream
+    "i2sdf_shade_sample": (C.c_int, [_P] * 7 + [C.POINTER(C.c_uint64), _I64, _I32] + [_P] * 4),
+    # view_direction, normal, Kd, Ks, rough, samples, seed (host), radiance, radiance_scale, bn, spp, colorDiffuse, colorSpec, stream
+    "i2sdf_shade_reduce": (C.c_int, [_P] * 6 + [C.POINTER(C.c_uint64), _P, _P, _I64, _I32] + [_P] * 3),
+    "i2sdf_shade_backward_workspace_bytes": (_I64, [_I64, _I32]),
+    # view_direction, normal, Kd, Ks, rough, samples, seed (host), radiance, radiance_scale, g_colorDiffuse, g_colorSpec, g_direction,
+    # g_points, bn, spp, workspace, gKd, gKs, grough, g_radiance, g_radiance_scale, stream
+    "i2sdf_shade_backward": (C.c_int, [_P] * 6 + [C.POINTER(C.c_uint64)] + [_P] * 6 + [_I64, _I32] + [_P] * 7),
     "i2sdf_light_forward": (C.c_int, [_P, _P, _P, _I64, _I64, _P, _P, _P]),
     "i2sdf_light_backward": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _P, _P, _P]),
     "i2sdf_loss_scratch_floats": (_I64, []),

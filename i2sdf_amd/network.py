@@ -513,6 +513,32 @@ class I2SDFNetwork(nn.Module):
         self.last_sampler_iters = iters
         return self.render(input, cam, dirs, dnorm, z_all, z_eik, predict_only, draws, _fresh=False)
 
+    @torch.no_grad()
+    def get_incident_radiance(self, pts: torch.Tensor, dirs: torch.Tensor, intersect_func=None) -> torch.Tensor:
+        """Radiance arriving at `pts` (n, 3) from the unit directions `dirs` (n, 3): what i2sdf_amd.RenderingLayer asks its model for.
+        The reference calls this method and never released it; here it is DEFINED as `rgb_values` (n, 3) of a `predict_only` render of
+        the rays with origin pts and direction dirs by the eval sampler -- `self.eval()({"uv": ..., "rays": {"cam_loc": pts, "dirs": dirs,
+        "dnorm": ones(n)}}, predict_only=True)["rgb_values"]`, bit for bit -- under no_grad, whatever mode the module is in, and in ONE
+        chunk per call (the layer already splits its rays).  The sampler's near bound applies from `pts` on, so the layer's 0.01 offset
+        along the direction is what keeps a ray off its own surface.  Every ray is sampled on [near, 2 scene_bounding_sphere] from its
+        origin, as every camera ray is (the sampler intersects no sphere without a background network), so an origin outside the bounding
+        sphere is not an error and not a special case: where the ray misses the scene the weights vanish and the radiance is ~0, the
+        counterpart of the (0, 0) interval i2sdf_sphere_intersections gives a miss.
+        `intersect_func` (the reference's hook for an external ray caster) is not supported: anything but None is refused."""
+        if intersect_func is not None:
+            raise NotImplementedError("get_incident_radiance: intersect_func is not supported (the secondary rays are rendered by the volume "
+                                      "renderer itself, there is no external ray caster to call)")
+        if pts.dim() != 2 or pts.shape[1] != 3 or dirs.shape != pts.shape:
+            raise ValueError(f"get_incident_radiance: pts {tuple(pts.shape)} and dirs {tuple(dirs.shape)} must both be (n, 3)")
+        pts, dirs = pts.detach().to(torch.float32).contiguous(), dirs.detach().to(torch.float32).contiguous()
+        rays = {"cam_loc": pts, "dirs": dirs, "dnorm": torch.ones(pts.shape[0], dtype=torch.float32, device=pts.device)}
+        was_training = self.training
+        self.train(False)
+        try:
+            return self.forward({"uv": pts, "rays": rays}, predict_only=True)["rgb_values"]
+        finally:
+            self.train(was_training)
+
     def _extra_mask(self, dev):
         m = getattr(self, "_extra_mask_t", None)
         if m is None or m.device != dev:

@@ -1013,6 +1013,66 @@ int i2sdf_depth_unproject_write(const float* depth, const float* intrinsics, con
                                 float lo, float hi, const void* workspace, int64_t n_points, int64_t* pointlinks, int64_t* pixlinks,
                                 float* pointcloud, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Surface shading -- RenderingLayer.forward (model/rendering/__init__.py) around its model call, with the parts of the BRDF library
+ * it uses (model/rendering/brdf.py: create_frame, probabilityToSampleSpecular, square_to_cosine_hemisphere, sample_ggx_specular,
+ * pdf_ggx, eval_ggx).  csrc/shade.hip; the per-sample arithmetic is csrc/brdf_dev.h, shared by host and device.  No plan: the layer
+ * does not depend on the networks.  All tensors fp32, contiguous, device; per-point inputs (bn, 3), rough (bn, 1).
+ *
+ * Per point:
+ *   frame   z = n / max(|n|, 1e-6);  s = z_z >= 0 ? 1 : -1;  a = -1 / (s + z_z);  b = z_x z_y a;
+ *           x = (1 + s z_x^2 a, s b, -s z_x);  y = (b, s + z_y^2 a, -z_y)                              [Duff et al. 2017]
+ *   wi      = (x.v, y.v, z.v) of view_direction v;  wi_mask = wi_z >= 1e-5;  then wi_z = max(wi_z, 1e-5) and wi / max(|wi|, 1e-6)
+ *   pS      = lS / (lD + lS),  l = max(lum(K), 0.01),  lum(c) = 0.212671 r + 0.715160 g + 0.072169 b  (a constant of the backward)
+ * Per sample s of point p, uniforms (u0, u1, u2) in [0, 1), with sq(t) = sqrt(max(t, 1e-8)) and nrm(v) = v / max(|v|, 1e-8):
+ *   diffuse lobe iff u0 >= pS:   wo = (cos(2 pi u1) sq(u2), sin(2 pi u1) sq(u2), sq(max(1 - u2, 0)))
+ *   else, alpha = rough^2:       Vh = nrm(alpha wi_x, alpha wi_y, wi_z);  q = Vh_x^2 + Vh_y^2;
+ *                                T1 = q > 0 ? (-Vh_y, Vh_x, 0) / sq(q) : (1, 0, 0);  T2 = Vh x T1;
+ *                                t1 = sq(u1) cos(2 pi u2);  t2 = sq(u1) sin(2 pi u2);  t2 <- lerp(sq(1 - t1^2), t2, (1 + Vh_z) / 2);
+ *                                Nh = t1 T1 + t2 T2 + sq(max(1 - t1^2 - t2^2, 0)) Vh;  h = nrm(alpha Nh_x, alpha Nh_y, max(Nh_z, 0));
+ *                                wo = 2 (wi.h) h - wi                                       [Heitz 2018, visible normals]
+ *   direction = wo_x x + wo_y y + wo_z z (world);   points = surface_points + 0.01 direction
+ *   H = nrm(wi + wo);  A = max(alpha^2, 1e-5) (inside D only);  D = A / (pi ((A - 1) H_z^2 + 1)^2)
+ *   G1 = 2 / (sq((alpha^2 (1 - wi_z^2) + wi_z^2) / wi_z^2) + 1)
+ *   pdf = pS D G1 / (4 wi_z) + (1 - pS) wo_z / pi;  pdf = 1e-4 where wi_z <= 1e-4 or wo_z <= 1e-4;  pdf = max(pdf, 1e-5)
+ *   G2 = 1/2 / (wi_z sq(alpha^2 + wo_z (wo_z - alpha^2 wo_z)) + wo_z sq(alpha^2 + wi_z (wi_z - alpha^2 wi_z)))
+ *   F = Ks + (F90 - Ks) (1 - wo.H)^5,  F90 = min(25 lum(Ks), 1);   f_spec = wo_z < 1e-4 ? 1e-4 : F G2 D;   f_diff = Kd / pi
+ *   w = max(wo_z, 0) / pdf;   L = radiance[p spp + s] * radiance_scale (scale NULL: ones)
+ *   colorDiffuse[p] = mean_s f_diff w L;   colorSpec[p] = mean_s f_spec w L
+ * Uniforms: `samples` (bn, spp, 3) of the caller, or drawn in the kernels from `seed` (HOST pointer to the 64-bit seed, read during
+ *   the call): Philox4x32-10, counter (p spp + s, 0, 8, 0), key (lo32(seed), hi32(seed)), u_k = (word_k >> 8) 2^-24 of words 0, 1, 2.
+ *   Exactly one of samples / seed is given.  i2sdf_shade_draws writes the uniforms a seed stands for.
+ * i2sdf_shade_sample:   direction, points (bn spp, 3), wi_mask (bn) bytes 0 / 1.
+ * i2sdf_shade_reduce:   colorDiffuse, colorSpec (bn, 3) from radiance (bn spp, 3) and radiance_scale (3) or NULL.  Nothing per-sample
+ *   is kept between the calls: wo, pdf and f are recomputed from the same uniforms.  Summation order: with G the smallest power of two
+ *   >= min(spp, 64), lane j of G takes samples j, j + G, ... in order, then the G partial sums meet in a butterfly (distance G/2, ..., 1):
+ *   fixed, no atomics, bitwise reproducible.
+ * i2sdf_shade_backward: upstream g_colorDiffuse, g_colorSpec (bn, 3) give gKd, gKs (bn, 3), grough (bn, 1), optionally g_radiance
+ *   (bn spp, 3, the gradient by `radiance` before the scale) and g_radiance_scale (3): per-workgroup partial sums in fixed slots of
+ *   `workspace` (i2sdf_shade_backward_workspace_bytes(bn, spp) bytes; 0 for sizes outside the limits), summed by a second one-workgroup
+ *   pass.  g_direction / g_points (bn spp, 3; each may be NULL) are the gradients a differentiable model returns for the rays: they
+ *   add (g_direction + 0.01 g_points) . d direction / d rough to grough.  Either group of upstream gradients may be absent -- the
+ *   colour group (g_colorDiffuse, g_colorSpec, radiance, gKd, gKs: all or none) or the ray group -- but not both; without the colour
+ *   group gKd / gKs are not written and g_radiance / g_radiance_scale must be NULL.  d / d rough follows wo through alpha, as the
+ *   reference's autograd does; a clamp passes the derivative where torch.clamp does (bound included); pS is a constant.  normal,
+ *   view_direction and surface_points get no gradient: the geometry is frozen at this stage.
+ * Limits (checked on the host before any launch, I2SDF_EINVAL with the reason in i2sdf_last_hip_error()): bn >= 0 (0: nothing is
+ *   launched), spp >= 1, bn spp < 2^31, no required pointer NULL, exactly one of samples / seed.
+ * ---------------------------------------------------------------------------------------------- */
+int i2sdf_shade_draws(uint64_t seed, int64_t bn, int32_t spp, float* samples, void* stream);
+int i2sdf_shade_sample(const float* surface_points, const float* view_direction, const float* normal, const float* Kd, const float* Ks,
+                       const float* rough, const float* samples, const uint64_t* seed, int64_t bn, int32_t spp, float* direction,
+                       float* points, uint8_t* wi_mask, void* stream);
+int i2sdf_shade_reduce(const float* view_direction, const float* normal, const float* Kd, const float* Ks, const float* rough,
+                       const float* samples, const uint64_t* seed, const float* radiance, const float* radiance_scale, int64_t bn,
+                       int32_t spp, float* colorDiffuse, float* colorSpec, void* stream);
+int64_t i2sdf_shade_backward_workspace_bytes(int64_t bn, int32_t spp);
+int i2sdf_shade_backward(const float* view_direction, const float* normal, const float* Kd, const float* Ks, const float* rough,
+                         const float* samples, const uint64_t* seed, const float* radiance, const float* radiance_scale,
+                         const float* g_colorDiffuse, const float* g_colorSpec, const float* g_direction, const float* g_points,
+                         int64_t bn, int32_t spp, void* workspace, float* gKd, float* gKs, float* grough, float* g_radiance,
+                         float* g_radiance_scale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
