@@ -34,6 +34,9 @@ def __getattr__(name):
     if name in ("RenderingLayer", "get_rendering_parameters", "shade_draws"):
         from . import shading
         return getattr(shading, name)
+    if name in ("KMeans", "kmeans_pp_centroid"):
+        from . import cluster
+        return getattr(cluster, name)
     if name == "RenderEngine":
         from .engine import RenderEngine
         return RenderEngine

@@ -86,6 +86,7 @@ IMAGE_STATS = 8                  # I2SDF_IMAGE_STATS
 SSIM_TILE_X, SSIM_TILE_Y = 32, 16    # I2SDF_SSIM_TILE_X, I2SDF_SSIM_TILE_Y
 BUBBLE_MAX_K = 4096              # I2SDF_BUBBLE_MAX_K
 BUBBLE_WS_PASSES_OFFSET = 24     # I2SDF_BUBBLE_WS_PASSES_OFFSET
+KMEANS_MAX_K = 256               # I2SDF_KMEANS_MAX_K
 
 
 class I2SDFError(RuntimeError):
@@ -247,6 +248,13 @@ SIGNATURES = {
     # view_direction, normal, Kd, Ks, rough, samples, seed (host), radiance, radiance_scale, g_colorDiffuse, g_colorSpec, g_direction,
     # g_points, bn, spp, workspace, gKd, gKs, grough, g_radiance, g_radiance_scale, stream
     "i2sdf_shade_backward": (C.c_int, [_P] * 6 + [C.POINTER(C.c_uint64)] + [_P] * 6 + [_I64, _I32] + [_P] * 7),
+    "i2sdf_kmeans_workspace_bytes": (_I64, [_I64, _I64]),
+    # points, n, k, seed, workspace, idx_out, centroids_out, stream
+    "i2sdf_kmeans_pp": (C.c_int, [_P, _I64, _I64, C.c_uint64, _P, _P, _P, _P]),
+    # points, n, k, centroids (in / out), max_iter, tol, workspace, labels, n_iter (device), stream
+    "i2sdf_kmeans_fit": (C.c_int, [_P, _I64, _I64, _P, _I32, _D, _P, _P, _P, _P]),
+    # points, n, centroids, k, labels, dist2, stream
+    "i2sdf_kmeans_assign": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _P]),
     "i2sdf_light_forward": (C.c_int, [_P, _P, _P, _I64, _I64, _P, _P, _P]),
     "i2sdf_light_backward": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _P, _P, _P]),
     "i2sdf_loss_scratch_floats": (_I64, []),

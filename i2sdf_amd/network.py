@@ -388,6 +388,28 @@ class I2SDFNetwork(nn.Module):
     def get_param_groups(self, lr):
         return [{"params": self.parameters(), "lr": lr}]
 
+    def init_emission_groups(self, n_emitters: int, pointcloud: torch.Tensor, init_emission: float = 1.0, use_dbscan: bool = False,
+                             seed: Optional[int] = None):
+        """model/network/__init__.py:49-75: cluster the emitter point cloud (n, 3) -- the light-mask pixels un-projected by depth -- into
+        n_emitters groups and create the trainable `emissions` (n_emitters, 3) = init_emission.  -> (labels (n,) int64, centroids
+        (n_emitters, 3)); the clustering stays in `self.emitter_clusters` (i2sdf_amd.cluster.KMeans: `.predict`, `.centroids`).
+
+        The seeds are k-means++ draws on the device (`seed`: 64 bits, None takes 62 bits from torch's CPU generator), or with use_dbscan
+        the reference's host-side route (i2sdf_amd.cluster.dbscan_seeds; needs scikit-learn).  Lloyd's iteration runs on the device
+        either way.  `emissions` is created on the module's device (the reference leaves it on the CPU), is in state_dict() under the
+        reference's key and in get_param_groups(), and is NOT part of the flat parameter buffer: no render or loss route reads it."""
+        from .cluster import KMeans, dbscan_seeds, kmeans_pp_centroid
+        dev = self._param_list()[0].device
+        if use_dbscan:
+            init_centroids = dbscan_seeds(pointcloud, n_emitters).to(pointcloud.device)
+        else:
+            init_centroids = kmeans_pp_centroid(pointcloud, n_emitters, seed)
+        clusters = KMeans(n_emitters)
+        labels = clusters.fit_predict(pointcloud, init_centroids)
+        emissions = nn.Parameter(torch.full((int(n_emitters), 3), float(init_emission), dtype=torch.float32, device=dev), True)
+        self.emitter_clusters, self.emissions = clusters, emissions      # (only now: a refused call leaves the module as it was)
+        return labels, clusters.centroids
+
     def sync_view_embed(self):
         """Hand the Fourier view embedder's matrix B (rendering_network.embedview_fn.B) to the plan of every engine built so far.  Done
         when an engine is built and after load_state_dict -- NOT per step: B is a constant of the net.  Call it after writing to the buffer

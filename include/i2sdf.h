@@ -1073,6 +1073,62 @@ int i2sdf_shade_backward(const float* view_direction, const float* normal, const
                          int64_t bn, int32_t spp, void* workspace, float* gKd, float* gKs, float* grough, float* g_radiance,
                          float* g_radiance_scale, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Emitter clustering -- I2SDFNetwork.init_emission_groups (model/network/__init__.py:49-75): k-means++ seeding
+ * (utils.kmeans_pp_centroid, utils/__init__.py:111-123) and Lloyd's iteration (fast_pytorch_kmeans.KMeans.fit_predict) of a point cloud
+ * on the device.  csrc/kmeans.hip.  No plan.  Every call only enqueues on `stream`: no allocation, no synchronisation, no host read;
+ * no floating-point atomic, so every result is bitwise reproducible.
+ *
+ * points (n, 3) fp32, 1 <= k <= n < 2^31, k <= I2SDF_KMEANS_MAX_K.  The squared distance of a point to a centroid is the direct form
+ *   ((x - cx)^2 + (y - cy)^2) + (z - cz)^2, every operation rounded to fp32 and none contracted into an FMA.  (The reference forms
+ *   2ab - a^2 - b^2 in Lloyd; its cancellation is not imitated.)
+ *
+ * Seeding (i2sdf_kmeans_pp).  The law is the reference's: each next centroid is a data point drawn with probability proportional to its
+ *   distance (not its squared distance) to the nearest centroid chosen so far.  The random stream is not numpy's: an exponential race on
+ *   Philox4x32-10 with key (lo32(seed), hi32(seed)) and stream word 9 (1..6: the training draws, 7: the bubble sampler, 8: shading).
+ *   round 0:        x = word 0 of counter (0, 0, 9, 0);  j_0 = (uint64(x) n) >> 32.
+ *   round i = 1..k-1: d_j = min(d_j, sqrtf(dist2(p_j, c_{i-1}))) in fp32, d starting at +inf;
+ *                   key_j = min(E_j / d_j, FLT_MAX), E_j = -log1pf(-v_j), v_j = ((float)x_j + 0.5f) 2^-32 (i2sdf_bubble_sample's key with
+ *                   weight d_j), x_j = word (j & 3) of counter (lo32(j >> 2), hi32(j >> 2), 9, i);
+ *                   point j is eligible iff 0 < d_j < inf;  j_i = the eligible j with the smallest (uint64(bits(key_j)) << 32) | j, so
+ *                   ties go to the lowest index;  nothing eligible (every distance 0: more centroids than distinct points): j_i = 0,
+ *                   the reference's argmax of an all-false mask.
+ *   Outputs: idx_out (k) int64 = j_0 .. j_{k-1}, centroids_out (k, 3) = points[idx_out].
+ *   Cost: one launch per round, one pass over the points each (12 B of point and 4 B of d read, 4 B of d written per point; d lives in
+ *   the workspace), ending in one 64-bit integer atomicMin per workgroup into the round's own slot, which the next round's launch reads.
+ *
+ * Lloyd (i2sdf_kmeans_fit): fit_predict of fast-pytorch-kmeans 0.1.9 with its defaults (euclidean, no minibatch), restated from its
+ *   source; the restatement has NOT been checked against the library itself (it is not installed where this project is developed).
+ *   Per iteration, with c the current centroids (in: the initial ones, out: the final ones):
+ *     1. labels_j = the index of the nearest centroid by dist2, the lowest index on ties (and for a point whose distances are all NaN);
+ *     2. c_new    = the mean of each cluster's points; an empty cluster gets (0, 0, 0) (the library's nan_to_num);
+ *     3. error    = sum over all 3k values of (c_new - c)^2  (fp64 of the fp32 values, fixed-order tree sum);
+ *     4. c = c_new;   5. stop after this iteration iff error <= tol.      At most max_iter iterations (the library: 100, tol 1e-4).
+ *   So the returned labels are those of the last iteration that ran: they belong to the centroids BEFORE the final update, as in the
+ *   library.  *n_iter (device int32) = iterations that ran.  The stop is a device flag: 2 max_iter launches are always enqueued, and
+ *   once the flag is set the remaining ones return at once.
+ *   Sums: 64-bit integer FIXED POINT.  With m the largest finite |coordinate| of the cloud (found by a pass of its own at the start of
+ *   the call) and 2^(e-1) <= m < 2^e, a coordinate x adds llrint(x 2^(31-e)) to its cluster's sum (|.| <= 2^31, so fewer than 2^31
+ *   points stay below 2^62); integer adds commute, so per-workgroup LDS sums and one global integer atomic per non-empty (cluster,
+ *   component, workgroup) give sums that do not depend on arrival order.  A coordinate below m 2^-8 in magnitude is rounded to a
+ *   multiple of m 2^-31 (at most half of that off); mean = double(sum) 2^(e-31) / count, rounded once to fp32.  A non-finite coordinate
+ *   adds 0 to the sum (its point still counts).
+ * i2sdf_kmeans_assign: step 1 alone on any points (KMeans.predict), dist2 (n) = the squared distance to the chosen centroid, or NULL.
+ *   Here k may exceed n (a few new points against many centroids); n = 0 is a no-op returning I2SDF_OK.
+ * workspace: i2sdf_kmeans_workspace_bytes(n, k) bytes (0 for sizes outside the limits), 16-byte aligned, shared by _pp and _fit; each
+ *   call clears what it reads on `stream`, so the contents before a call do not matter.
+ * Limits, checked on the host before any launch (I2SDF_EINVAL): the sizes above, no pointer NULL (dist2 excepted), max_iter >= 1,
+ *   tol >= 0 and not NaN, workspace alignment.
+ * Not imitated: minibatch k-means, cosine mode, dimensions other than 3, numpy's random stream.
+ * ---------------------------------------------------------------------------------------------- */
+#define I2SDF_KMEANS_MAX_K 256
+int64_t i2sdf_kmeans_workspace_bytes(int64_t n, int64_t k);
+int i2sdf_kmeans_pp(const float* points, int64_t n, int64_t k, uint64_t seed, void* workspace, int64_t* idx_out, float* centroids_out,
+                    void* stream);
+int i2sdf_kmeans_fit(const float* points, int64_t n, int64_t k, float* centroids, int32_t max_iter, double tol, void* workspace,
+                     int64_t* labels, int32_t* n_iter, void* stream);
+int i2sdf_kmeans_assign(const float* points, int64_t n, const float* centroids, int64_t k, int64_t* labels, float* dist2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
