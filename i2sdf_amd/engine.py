@@ -573,10 +573,19 @@ class RenderEngine:
                                                L.ptr(d["eik_idx"]), L.ptr(d["eik_pts"]), L.ptr(d["nbr_off"]), L.stream_ptr()), "i2sdf_training_draws")
         return d
 
-    def sample_rays(self, flat_params, cam, dirs, training=False, strat_u=None, cdf_u=None, extra_idx=None, eik_idx=None, force_iters=0):
-        """ErrorBoundSampler.get_z_vals on the device.  Returns z_all (B, N_samples+N_extra+2), z_eik (B,1), iters (device int32)."""
+    def sample_rays(self, flat_params, cam, dirs, training=False, strat_u=None, cdf_u=None, extra_idx=None, eik_idx=None, force_iters=0,
+                    workspace=None):
+        """ErrorBoundSampler.get_z_vals on the device.  Returns z_all (B, N_samples+N_extra+2), z_eik (B,1), iters (device int32).
+        `workspace`: a contiguous fp32 device tensor of at least i2sdf_sampler_workspace_floats(B) elements to run the loop in (the tests
+        pre-fill one and look at what the loop left untouched); None allocates one."""
         B, dev = cam.shape[0], cam.device
-        ws = torch.empty(int(self._lib.i2sdf_sampler_workspace_floats(B)), dtype=torch.float32, device=dev)
+        n_ws = int(self._lib.i2sdf_sampler_workspace_floats(B))
+        if workspace is None:
+            ws = torch.empty(n_ws, dtype=torch.float32, device=dev)
+        else:
+            ws = workspace
+            if not (ws.is_cuda and ws.device == dev and ws.dtype == torch.float32 and ws.is_contiguous() and ws.numel() >= n_ws):
+                raise ValueError(f"workspace must be a contiguous fp32 tensor of at least {n_ws} elements on {dev}")
         z_out = torch.empty(B, self.n_z, dtype=torch.float32, device=dev)
         z_eik = torch.empty(B, 1, dtype=torch.float32, device=dev)
         iters = torch.empty(1, dtype=torch.int32, device=dev) if B > 0 else torch.zeros(1, dtype=torch.int32, device=dev)      # written by the final kernel

@@ -516,6 +516,12 @@ typedef struct i2sdf_sampler_cfg {
 int i2sdf_error_bound(const float* z, const float* sdf, int64_t B, int32_t n, const float* beta, int64_t ldbeta,
                       const float* d_star_in, float* d_star_out, float* bound, void* stream);
 
+/* The workspace of i2sdf_sample_rays, in floats.  Its layout is what the stage tests read (tests/sampler_ref.py), so it is fixed:
+ * six row buffers of B*640 -- depths zA, zB, sdf values sA, sB, int32 merge indices iA, iB (iteration it, counted from 0, reads its row
+ * from zA/sA when `it` is even and from zB/sB when odd, with the indices that produced it in iB / iA) --, then `samples` (B rows of 128:
+ * the last inverse-CDF output), `sdf_new` (B*128 reserved, written packed as B rows of N_samples_eval), `beta` (B), 32 int32 state
+ * words (0: done, 1: iterations run, 2+it: beta > beta0 seen, 16+it: workgroups finished) and 64 spare floats.  Entries of a row past
+ * its current length, columns of `samples` past max(N_samples_eval, N_samples) and the spare floats are never written.           */
 int64_t i2sdf_sampler_workspace_floats(int64_t B);
 int i2sdf_sample_rays(const i2sdf_plan* plan, const float* packed, const float* params, const i2sdf_sampler_cfg* cfg,
                       const float* cam, const float* dirs, int64_t B, int32_t training, const float* t_lin, const float* u_more,

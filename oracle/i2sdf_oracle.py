@@ -508,6 +508,10 @@ class SamplerTrace:
     z_rows: List[Tensor] = field(default_factory=list)       # per iteration, the row the bound was evaluated on
     sdf_rows: List[Tensor] = field(default_factory=list)
     new_samples: List[Tensor] = field(default_factory=list)  # per iteration, inverse-CDF output
+    prior_betas: List[Tensor] = field(default_factory=list)  # per iteration, the beta the line search started from (B,); [0] = Lemma 2
+    sdf_new: List[Tensor] = field(default_factory=list)      # per iteration, sdf at the newest samples (B, N_samples_eval)
+    sort_idx: List[Tensor] = field(default_factory=list)     # per merge, the sort indices into cat([row, new samples]) (B, n)
+    stable_sort: bool = False                                # ask for a stable merge (ties: old sample first, new ones in order), as the device merges
 
 
 def sample_z_vals(sd, cfg: NetCfg, dirs: Tensor, cam_loc: Tensor, training: bool, draws: Optional[Draws] = None,
@@ -538,6 +542,8 @@ def sample_z_vals(sd, cfg: NetCfg, dirs: Tensor, cam_loc: Tensor, training: bool
             else:
                 sdf = s_new
             d = sdf.reshape(z_vals.shape)
+            if trace is not None:
+                trace.prior_betas.append(beta.clone()); trace.sdf_new.append(s_new.reshape(B, -1).clone())
             dists = z_vals[:, 1:] - z_vals[:, :-1]
             d_star = d_star_bound(z_vals, d)
             # line search on beta (ray_sampler.py:118-132)
@@ -587,7 +593,12 @@ def sample_z_vals(sd, cfg: NetCfg, dirs: Tensor, cam_loc: Tensor, training: bool
             if trace is not None:
                 trace.new_samples.append(samples.clone())
             if more:
-                z_vals, samples_idx = torch.sort(torch.cat([z_vals, samples], -1), -1)
+                if trace is not None and trace.stable_sort:
+                    z_vals, samples_idx = torch.sort(torch.cat([z_vals, samples], -1), dim=-1, stable=True)
+                else:
+                    z_vals, samples_idx = torch.sort(torch.cat([z_vals, samples], -1), -1)
+                if trace is not None:
+                    trace.sort_idx.append(samples_idx.clone())
         if trace is not None:
             trace.iters = total_iters
         near = torch.full((B, 1), sc.near, dtype=dtype, device=dev)
