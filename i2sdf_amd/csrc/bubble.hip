@@ -23,6 +23,7 @@
 #include <stdint.h>
 #include "../../include/i2sdf.h"
 #include "philox.h"
+#include "blockops.h"
 
 int i2sdf_hip_check(hipError_t e, const char* what);
 
@@ -30,9 +31,12 @@ namespace {
 
 using i2sdf_philox::U4;
 using i2sdf_philox::philox4x32_10;
+using i2sdf_philox::NOT_ELIGIBLE;
+using i2sdf_philox::KEY_MAX;
+using i2sdf_philox::key_bits;
+using i2sdf_blockops::block_excl_scan;
+using i2sdf_blockops::wave_incl_scan;
 
-constexpr unsigned NOT_ELIGIBLE = 0x7f800000u;      // bits(+inf); an eligible key is clamped to FLT_MAX = 0x7f7fffff
-constexpr unsigned KEY_MAX = 0x7f7fffffu;
 constexpr int THREADS = 256;
 constexpr int MAX_BLOCKS = 2048;                      // 256 CUs x 8 workgroups of 4 waves
 // digits of the select, most significant first (bit 31 of a key >= 0 is 0)
@@ -63,18 +67,8 @@ struct Src {
   int vec;              // w is 16-byte aligned: full quads are one load
 };
 
-// `above`: keys greater than this do not matter to the caller and may come back as NOT_ELIGIBLE.  E = -log1p(-v) >= v, so a key is
-// at least v / w: with v > 1.001 above w it exceeds `above` whatever the rounding of log1pf (2 ulp) and of the divide -- and then
-// neither is computed.  +inf as `above` drops nothing; a bound of FLT_MAX or more must be passed as +inf (above_of), because an
-// overflowing key is clamped to FLT_MAX and so does NOT exceed it.
+// a bound of FLT_MAX or more goes to key_bits (philox.h) as +inf: an overflowing key is clamped to FLT_MAX and so does NOT exceed it
 __device__ __forceinline__ float above_of(unsigned bits) { return bits >= KEY_MAX ? __builtin_inff() : __uint_as_float(bits); }
-__device__ __forceinline__ unsigned key_bits(unsigned x, float w, float above) {
-  if (!(w > 0.f && w < __builtin_inff())) return NOT_ELIGIBLE;
-  const float v = ((float)x + 0.5f) * 2.3283064365386963e-10f;      // 2^-32
-  if (v > 1.001f * (above * w)) return NOT_ELIGIBLE;
-  const float key = fminf(-log1pf(-v) / w, 3.4028234663852886e38f);
-  return __float_as_uint(key);
-}
 
 // keys of entries 4q .. 4q+3 (NOT_ELIGIBLE past n); false when none is eligible (Philox is skipped then)
 __device__ __forceinline__ bool quad_keys(const Src& s, int64_t q, float above, unsigned& b0, unsigned& b1, unsigned& b2, unsigned& b3) {
@@ -149,12 +143,7 @@ __global__ __launch_bounds__(64) void bubble_pick_kernel(State* __restrict__ st,
   if (lane == 0) st->passes += 1u;                       // this digit's histogram pass read the weights
   unsigned sum = 0;
   for (int j = 0; j < PER; ++j) sum += ghist[lane * PER + j];
-  unsigned incl = sum;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const unsigned up = __shfl_up(incl, d);
-    if (lane >= d) incl += up;
-  }
+  const unsigned incl = wave_incl_scan(sum, lane);
   const unsigned total = __shfl(incl, 63);
   if (TOP) {
     if (lane == 0) {
@@ -245,24 +234,6 @@ constexpr int UP_THREADS = 256, UP_PER = 4, UP_BLOCK = UP_THREADS * UP_PER;     
 
 __device__ __forceinline__ bool depth_ok(float d, float lo, float hi) { return d > lo && d < hi; }
 
-__device__ __forceinline__ int block_excl_scan(int v, int* total) {      // 256 threads
-  __shared__ int wsum[UP_THREADS / 64];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  int incl = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int up = __shfl_up(incl, d);
-    if (lane >= d) incl += up;
-  }
-  if (lane == 63) wsum[wv] = incl;
-  __syncthreads();
-  int base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < UP_THREADS / 64; ++w) { if (w < wv) base += wsum[w]; tot += wsum[w]; }
-  *total = tot;
-  return base + incl - v;
-}
-
 __global__ __launch_bounds__(UP_THREADS) void unproject_count_kernel(const float* __restrict__ depth, int64_t total, float lo, float hi,
                                                                      int32_t* __restrict__ counts, uint8_t* __restrict__ masks) {
   const int64_t p0 = (int64_t)blockIdx.x * UP_BLOCK + (int64_t)threadIdx.x * UP_PER;
@@ -275,7 +246,7 @@ __global__ __launch_bounds__(UP_THREADS) void unproject_count_kernel(const float
       c += ok ? 1 : 0;
     }
   int tot;
-  block_excl_scan(c, &tot);
+  (void)block_excl_scan<UP_THREADS>(c, tot);
   if (threadIdx.x == 0) counts[blockIdx.x] = tot;
 }
 
@@ -286,10 +257,9 @@ __global__ __launch_bounds__(UP_THREADS) void unproject_scan_kernel(const int32_
     const int64_t b = b0 + threadIdx.x;
     const int v = b < nb ? counts[b] : 0;
     int tot;
-    const int ex = block_excl_scan(v, &tot);
+    const int ex = block_excl_scan<UP_THREADS>(v, tot);
     if (b < nb) offsets[b] = carry + ex;
     carry += tot;
-    __syncthreads();                                     // (the scan's LDS slots are reused by the next round)
   }
   if (threadIdx.x == 0) offsets[nb] = carry;
 }
@@ -310,7 +280,7 @@ __global__ __launch_bounds__(UP_THREADS) void unproject_write_kernel(const float
     c += ok[e] ? 1 : 0;
   }
   int tot;
-  int64_t at = offsets[blockIdx.x] + block_excl_scan(c, &tot);
+  int64_t at = offsets[blockIdx.x] + block_excl_scan<UP_THREADS>(c, tot);
 #pragma unroll
   for (int e = 0; e < UP_PER; ++e) {
     const int64_t g = p0 + e;
@@ -343,10 +313,7 @@ bool unproject_sizes(int64_t n_img, int32_t H, int32_t W, int64_t& total, int64_
   return true;
 }
 
-unsigned stream_blocks(int64_t n) {
-  const int64_t nq = (n + 3) / 4, b = (nq + THREADS - 1) / THREADS;
-  return (unsigned)(b < 1 ? 1 : b > MAX_BLOCKS ? MAX_BLOCKS : b);
-}
+unsigned stream_blocks(int64_t n) { return i2sdf_blockops::blocks((n + 3) / 4, THREADS, MAX_BLOCKS); }      // a thread per quad
 
 Src make_src(const float* w, int64_t n, uint64_t seed, uint32_t draw) {
   return Src{w, n, (unsigned)seed, (unsigned)(seed >> 32), draw, ((uintptr_t)w & 15) == 0 ? 1 : 0};

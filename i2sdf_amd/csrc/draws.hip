@@ -17,9 +17,8 @@ namespace {
 
 using i2sdf_philox::U4;
 using i2sdf_philox::philox4x32_10;
+using i2sdf_philox::u01;
 constexpr int MAX_EXTRA_ROWS = 16, MAX_EXTRA = 128;      // sampler iterations / extra columns the k-subset thread supports
-
-__device__ __forceinline__ float u01(unsigned x) { return (float)(x >> 8) * 5.9604644775390625e-8f; }   // [0, 1), 24 bits like torch.rand
 
 struct DrawArgs {
   unsigned seed_lo, seed_hi;

@@ -42,12 +42,17 @@
 #include <math.h>
 #include <stdint.h>
 #include "../../include/i2sdf.h"
+#include "blockops.h"
 
 #pragma clang fp contract(off)
 
 int i2sdf_hip_check(hipError_t e, const char* what);
 
 namespace {
+
+using i2sdf_blockops::wave_max;
+using i2sdf_blockops::wave_min;
+using i2sdf_blockops::wave_sum;
 
 constexpr int IM_THREADS = 256;
 constexpr int IM_WAVES = IM_THREADS / 64;
@@ -81,22 +86,6 @@ bool plan(int32_t n_views, int32_t H, int32_t W, Plan& P) {
   P.off_ssim = (int64_t)n_views * P.sb * IM_STAT_SLOT * 8;
   P.bytes = P.off_ssim + (int64_t)n_views * P.tiles * 8;      // (monotone in n_views, H and W)
   return true;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-  for (int o = 32; o; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
 }
 
 // One wave.  The n slots are cut into 64 runs of ceil(n / 64) consecutive slots; lane l adds run l in index order, lane 0 adds the 64

@@ -4,7 +4,7 @@
 // i2sdf_kmeans_pp -- utils.kmeans_pp_centroid (utils/__init__.py:111-123): the next centroid is a data point drawn with probability
 // proportional to its distance to the nearest centroid so far.  The reference builds an (n, i, 3) tensor per round and blocks the host
 // on an argmax; here a round is ONE pass over the points (12 B of point and 4 B of d read, 4 B written): d_j = min(d_j, |p_j - c|), the
-// exponential-race key E_j / d_j of bubble.hip on Philox stream word 9, and the minimum of (key bits << 32 | j) -- a wave butterfly, four
+// exponential-race key E_j / d_j (philox.h, as bubble.hip) on Philox stream word 9, and the minimum of (key bits << 32 | j) -- a wave butterfly, four
 // values in LDS, one 64-bit integer atomicMin per workgroup into the round's own slot.  The next round's launch reads that slot: the
 // winner never reaches the host.
 //
@@ -21,6 +21,7 @@
 #include <stdint.h>
 #include "../../include/i2sdf.h"
 #include "philox.h"
+#include "blockops.h"
 
 int i2sdf_hip_check(hipError_t e, const char* what);
 
@@ -28,10 +29,14 @@ namespace {
 
 using i2sdf_philox::U4;
 using i2sdf_philox::philox4x32_10;
+using i2sdf_philox::NOT_ELIGIBLE;
+using i2sdf_philox::key_bits;
+using i2sdf_blockops::blocks;
+using i2sdf_blockops::wave_max;
+using i2sdf_blockops::wave_min;
 
-constexpr unsigned NOT_ELIGIBLE = 0x7f800000u;      // bits(+inf); an eligible key is clamped to FLT_MAX
 constexpr unsigned long long NO_WINNER = ~0ull;     // a slot no workgroup has written: nothing was eligible -> index 0
-constexpr unsigned STREAM_WORD = 9u;                // 1..6 draws.hip, 7 bubble.hip, 8 shade.hip
+constexpr unsigned STREAM_WORD = 9u;                // (philox.h lists the others)
 constexpr int THREADS = 256, WAVES = THREADS / 64;
 constexpr int MAX_BLOCKS_PP = 2048;                 // 256 CUs x 8 workgroups of 4 waves
 constexpr int MAX_BLOCKS_FIT = 1024;                // every workgroup ends in up to 4k global atomics: fewer, longer workgroups
@@ -48,14 +53,6 @@ constexpr int64_t OFF_ACC = sizeof(Head);
 inline int64_t off_slots(int64_t k) { return OFF_ACC + 32 * k; }
 inline int64_t off_d(int64_t k) { return (off_slots(k) + 8 * k + 15) / 16 * 16; }
 
-// bubble.hip's key: E / w with E = -log1pf(-v), v = (x + 0.5) 2^-32, clamped to FLT_MAX; w not in (0, inf) is not eligible
-__device__ __forceinline__ unsigned key_bits(unsigned x, float w) {
-  if (!(w > 0.f && w < __builtin_inff())) return NOT_ELIGIBLE;
-  const float v = ((float)x + 0.5f) * 2.3283064365386963e-10f;      // 2^-32
-  const float key = fminf(-log1pf(-v) / w, 3.4028234663852886e38f);
-  return __float_as_uint(key);
-}
-
 // (x-cx)^2 + (y-cy)^2 + (z-cz)^2, every operation rounded to fp32, summed left to right, nothing contracted into an FMA
 __device__ __forceinline__ float dist2(float x, float y, float z, float cx, float cy, float cz) {
   const float dx = __fsub_rn(x, cx), dy = __fsub_rn(y, cy), dz = __fsub_rn(z, cz);
@@ -63,16 +60,6 @@ __device__ __forceinline__ float dist2(float x, float y, float z, float cx, floa
 }
 
 __device__ __forceinline__ unsigned slot_index(unsigned long long s) { return s == NO_WINNER ? 0u : (unsigned)(s & 0xffffffffull); }
-
-__device__ __forceinline__ unsigned long long wave_min(unsigned long long v) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) {
-    const unsigned lo = __shfl_xor((unsigned)v, d), hi = __shfl_xor((unsigned)(v >> 32), d);
-    const unsigned long long o = ((unsigned long long)hi << 32) | lo;
-    v = o < v ? o : v;
-  }
-  return v;
-}
 
 // ---- seeding ------------------------------------------------------------------------------------
 __global__ void kmeans_pp_first_kernel(unsigned long long* __restrict__ slots, unsigned n, unsigned seed_lo, unsigned seed_hi) {
@@ -125,7 +112,7 @@ __global__ __launch_bounds__(THREADS) void kmeans_pp_round_kernel(const float* _
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       if (j + e >= n) continue;
-      const unsigned kb = key_bits(x[e], dj[e]);
+      const unsigned kb = key_bits(x[e], dj[e], __builtin_inff());      // every key matters: nothing dropped
       if (kb == NOT_ELIGIBLE) continue;
       const unsigned long long comp = ((unsigned long long)kb << 32) | (unsigned long long)(unsigned)(j + e);
       best = comp < best ? comp : best;
@@ -158,11 +145,7 @@ __global__ __launch_bounds__(THREADS) void kmeans_range_kernel(const float* __re
     const unsigned b = __float_as_uint(points[i]) & 0x7fffffffu;
     if (b < 0x7f800000u && b > m) m = b;
   }
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) {
-    const unsigned o = __shfl_xor(m, d);
-    m = o > m ? o : m;
-  }
+  m = wave_max(m);
   if ((threadIdx.x & 63) == 0 && m) atomicMax(&head->maxabs_bits, m);
 }
 
@@ -258,11 +241,6 @@ __global__ void kmeans_fit_begin_kernel(int32_t* __restrict__ n_iter) { *n_iter 
 
 bool sizes_ok(int64_t n, int64_t k) { return k >= 1 && k <= MAX_K && n >= 1 && n <= INT32_MAX; }
 
-unsigned blocks_for(int64_t items, int cap) {
-  const int64_t b = (items + THREADS - 1) / THREADS;
-  return (unsigned)(b < 1 ? 1 : b > cap ? cap : b);
-}
-
 }  // namespace
 
 extern "C" int64_t i2sdf_kmeans_workspace_bytes(int64_t n, int64_t k) {
@@ -283,7 +261,7 @@ extern "C" int i2sdf_kmeans_pp(const float* points, int64_t n, int64_t k, uint64
   const int vec = ((uintptr_t)points & 15) == 0 ? 1 : 0;                   // (d is 16-byte aligned by the layout)
   if (int rc = i2sdf_hip_check(hipMemsetAsync(slots, 0xff, (size_t)(8 * k), st), "kmeans_pp clear")) return rc;
   kmeans_pp_first_kernel<<<1, 1, 0, st>>>(slots, (unsigned)n, lo, hi);
-  const unsigned nb = blocks_for((n + 3) / 4, MAX_BLOCKS_PP);
+  const unsigned nb = blocks((n + 3) / 4, THREADS, MAX_BLOCKS_PP);
   for (int64_t i = 1; i < k; ++i) kmeans_pp_round_kernel<<<nb, THREADS, 0, st>>>(points, n, d, slots, (unsigned)i, lo, hi, vec);
   kmeans_pp_emit_kernel<<<1, THREADS, 0, st>>>(points, slots, (int)k, idx_out, centroids_out);
   return i2sdf_hip_check(hipGetLastError(), "kmeans_pp");
@@ -300,8 +278,8 @@ extern "C" int i2sdf_kmeans_fit(const float* points, int64_t n, int64_t k, float
   unsigned long long* acc = (unsigned long long*)(ws + OFF_ACC);
   if (int rc = i2sdf_hip_check(hipMemsetAsync(ws, 0, (size_t)off_slots(k), st), "kmeans_fit clear")) return rc;
   kmeans_fit_begin_kernel<<<1, 1, 0, st>>>(n_iter);
-  kmeans_range_kernel<<<blocks_for(3 * n, MAX_BLOCKS_FIT), THREADS, 0, st>>>(points, 3 * n, head);
-  const unsigned nb = blocks_for(n, MAX_BLOCKS_FIT);
+  kmeans_range_kernel<<<blocks(3 * n, THREADS, MAX_BLOCKS_FIT), THREADS, 0, st>>>(points, 3 * n, head);
+  const unsigned nb = blocks(n, THREADS, MAX_BLOCKS_FIT);
   for (int32_t it = 0; it < max_iter; ++it) {
     kmeans_assign_kernel<true><<<nb, THREADS, 0, st>>>(points, n, centroids, (int)k, labels, nullptr, head, acc);
     kmeans_update_kernel<<<1, THREADS, 0, st>>>(head, acc, centroids, (int)k, tol, n_iter);
@@ -314,7 +292,7 @@ extern "C" int i2sdf_kmeans_assign(const float* points, int64_t n, const float* 
   if (k < 1 || k > MAX_K || n < 0 || n > INT32_MAX) return I2SDF_EINVAL;
   if (n == 0) return I2SDF_OK;
   if (points == nullptr || centroids == nullptr || labels == nullptr) return I2SDF_EINVAL;
-  kmeans_assign_kernel<false><<<blocks_for(n, MAX_BLOCKS_PP), THREADS, 0, (hipStream_t)stream>>>(points, n, centroids, (int)k, labels, dist2,
+  kmeans_assign_kernel<false><<<blocks(n, THREADS, MAX_BLOCKS_PP), THREADS, 0, (hipStream_t)stream>>>(points, n, centroids, (int)k, labels, dist2,
                                                                                                nullptr, nullptr);
   return i2sdf_hip_check(hipGetLastError(), "kmeans_assign");
 }

@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/i2sdf.h"
+#include "blockops.h"
 
 // every product and sum rounded on its own, like the numpy restatement of the tests (no fused multiply-adds)
 #pragma clang fp contract(off)
@@ -22,11 +23,11 @@ int i2sdf_hip_check(hipError_t e, const char* what);
 
 namespace {
 
+using namespace i2sdf_blockops;
+
 #include "mcubes_tables.inc"
 
 constexpr int MC_THREADS = 256;                  // lattice points per classify / emit block
-constexpr int SCAN_ITEMS = 4;
-constexpr int SCAN_CHUNK = MC_THREADS * SCAN_ITEMS;   // block pairs per scan workgroup
 
 struct Vol {
   const float* v;
@@ -68,82 +69,19 @@ __device__ __forceinline__ int cell_case(const Vol& V, int64_t p, int i, int j, 
   return cs;
 }
 
-__device__ __forceinline__ int64_t wave_incl(int64_t x, int lane) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int64_t y = __shfl_up(x, d, 64);
-    if (lane >= d) x += y;
-  }
-  return x;
-}
-
-// exclusive prefix of x over the block's 256 threads (thread order); `total` = the block's sum
-__device__ int64_t block_excl(int64_t x, int64_t& total) {
-  __shared__ int64_t ws[MC_THREADS / 64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int64_t inc = wave_incl(x, lane);
-  if (lane == 63) ws[w] = inc;
-  __syncthreads();
-  int64_t base = 0, tot = 0;
-#pragma unroll
-  for (int u = 0; u < MC_THREADS / 64; ++u) {
-    if (u < w) base += ws[u];
-    tot += ws[u];
-  }
-  __syncthreads();                               // ws is reused by the next call
-  total = tot;
-  return base + inc - x;
-}
-
 __global__ __launch_bounds__(MC_THREADS) void mc_classify(Vol V, longlong2* __restrict__ blk) {
   const int64_t p = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
-  int64_t nv = 0, nt = 0;
+  longlong2 c = make_longlong2(0, 0);             // (vertices, triangles) of this point
   if (p < V.n) {
     int i, j, k;
     unflatten(V, p, i, j, k);
-    nv = __popc(edge_mask(V, p, i, j, k));
+    c.x = __popc(edge_mask(V, p, i, j, k));
     const int cs = cell_case(V, p, i, j, k);
-    if (cs >= 0) nt = kMcNumTri[cs];
+    if (cs >= 0) c.y = kMcNumTri[cs];
   }
-  int64_t sv, st;
-  (void)block_excl(nv, sv);
-  (void)block_excl(nt, st);
-  if (threadIdx.x == 0) blk[blockIdx.x] = make_longlong2(sv, st);
-}
-
-// sums[b] = a[b*SCAN_CHUNK .. (b+1)*SCAN_CHUNK) summed
-__global__ __launch_bounds__(MC_THREADS) void mc_scan_reduce(const longlong2* __restrict__ a, int64_t n, longlong2* __restrict__ sums) {
-  const int64_t base = (int64_t)blockIdx.x * SCAN_CHUNK + threadIdx.x * SCAN_ITEMS;
-  int64_t x = 0, y = 0;
-#pragma unroll
-  for (int u = 0; u < SCAN_ITEMS; ++u)
-    if (base + u < n) { x += a[base + u].x; y += a[base + u].y; }
-  int64_t sx, sy;
-  (void)block_excl(x, sx);
-  (void)block_excl(y, sy);
-  if (threadIdx.x == 0) sums[blockIdx.x] = make_longlong2(sx, sy);
-}
-
-// a[chunk b] <- exclusive prefix within the chunk + add[b] (add NULL: 0); total (one workgroup only): the sum of everything
-__global__ __launch_bounds__(MC_THREADS) void mc_scan_chunks(longlong2* __restrict__ a, int64_t n, const longlong2* __restrict__ add,
-                                                             longlong2* __restrict__ total) {
-  const int64_t base = (int64_t)blockIdx.x * SCAN_CHUNK + threadIdx.x * SCAN_ITEMS;
-  longlong2 it[SCAN_ITEMS];
-  int64_t x = 0, y = 0;
-#pragma unroll
-  for (int u = 0; u < SCAN_ITEMS; ++u) {
-    it[u] = base + u < n ? a[base + u] : make_longlong2(0, 0);
-    x += it[u].x; y += it[u].y;
-  }
-  int64_t tx, ty;
-  int64_t ox = block_excl(x, tx), oy = block_excl(y, ty);
-  if (add) { ox += add[blockIdx.x].x; oy += add[blockIdx.x].y; }
-#pragma unroll
-  for (int u = 0; u < SCAN_ITEMS; ++u) {
-    if (base + u < n) a[base + u] = make_longlong2(ox, oy);
-    ox += it[u].x; oy += it[u].y;
-  }
-  if (total && threadIdx.x == 0) *total = make_longlong2(tx, ty);
+  longlong2 tot;
+  (void)block_excl_scan<MC_THREADS>(c, tot);
+  if (threadIdx.x == 0) blk[blockIdx.x] = tot;
 }
 
 // np.gradient(vol, *spacing) at one point: central differences over 2*spacing, one-sided on the border
@@ -168,8 +106,8 @@ __global__ __launch_bounds__(MC_THREADS) void mc_emit_verts(Vol V, Geo G, const 
     unflatten(V, p, i, j, k);
     m = edge_mask(V, p, i, j, k);
   }
-  int64_t tot;
-  int64_t off = block_excl(__popc(m), tot) + blk[blockIdx.x].x;
+  int tot;
+  int64_t off = block_excl_scan<MC_THREADS>((int)__popc(m), tot) + blk[blockIdx.x].x;
   if (p >= V.n) return;
   pofs[p] = (int32_t)off;
   pmask[p] = (uint8_t)m;
@@ -208,8 +146,8 @@ __global__ __launch_bounds__(MC_THREADS) void mc_emit_faces(Vol V, const longlon
     cs = cell_case(V, p, i, j, k);
   }
   const int nt = cs >= 0 ? kMcNumTri[cs] : 0;
-  int64_t tot;
-  const int64_t off = block_excl(nt, tot) + blk[blockIdx.x].y;
+  int tot;
+  const int64_t off = block_excl_scan<MC_THREADS>(nt, tot) + blk[blockIdx.x].y;
   for (int s = 0; s < nt; ++s) {
     if (off + s >= cap_f) return;
     for (int c = 0; c < 3; ++c) {
@@ -225,11 +163,8 @@ __global__ __launch_bounds__(MC_THREADS) void mc_emit_faces(Vol V, const longlon
 struct Layout {
   int64_t n, nb0;
   int64_t off_pofs, off_mask, off_total, bytes;
-  int n_levels;
-  int64_t level_off[8], level_n[8];
+  ScanLevels scan;                               // level 0: the nb0 block pairs
 };
-
-int64_t align16(int64_t x) { return (x + 15) / 16 * 16; }
 
 bool layout(int32_t nx, int32_t ny, int32_t nz, Layout& L) {
   if (nx < 2 || ny < 2 || nz < 2) return false;
@@ -239,17 +174,9 @@ bool layout(int32_t nx, int32_t ny, int32_t nz, Layout& L) {
   int64_t o = 0;
   L.off_pofs = o; o = align16(o + 4 * L.n);
   L.off_mask = o; o = align16(o + L.n);
-  L.n_levels = 0;
-  for (int64_t m = L.nb0;; m = (m + SCAN_CHUNK - 1) / SCAN_CHUNK) {
-    if (L.n_levels == 8) return false;
-    L.level_off[L.n_levels] = o;
-    L.level_n[L.n_levels] = m;
-    ++L.n_levels;
-    o += 16 * m;
-    if (m <= SCAN_CHUNK) break;
-  }
-  L.off_total = o; o += 16;
-  L.bytes = o;
+  if (!scan_levels(L.nb0, sizeof(longlong2), o, L.scan)) return false;
+  L.off_total = L.scan.bytes;
+  L.bytes = L.off_total + 16;
   return true;
 }
 
@@ -267,22 +194,10 @@ extern "C" int i2sdf_marching_cubes_count(const float* vol, int32_t nx, int32_t 
   hipStream_t st = (hipStream_t)stream;
   char* ws = (char*)workspace;
   const Vol V{vol, nx, ny, nz, (int64_t)ny * nz, nz, L.n, level};
-  longlong2* lv[8];
-  for (int l = 0; l < L.n_levels; ++l) lv[l] = (longlong2*)(ws + L.level_off[l]);
   longlong2* total = (longlong2*)(ws + L.off_total);
-  mc_classify<<<(unsigned)L.nb0, MC_THREADS, 0, st>>>(V, lv[0]);
+  mc_classify<<<(unsigned)L.nb0, MC_THREADS, 0, st>>>(V, (longlong2*)(ws + L.scan.level_off[0]));
   if (int rc = i2sdf_hip_check(hipGetLastError(), "mc_classify")) return rc;
-  // reduce up the levels, scan the top one in a single workgroup, then scan every lower level with its chunk offsets
-  for (int l = 0; l + 1 < L.n_levels; ++l) {
-    mc_scan_reduce<<<(unsigned)L.level_n[l + 1], MC_THREADS, 0, st>>>(lv[l], L.level_n[l], lv[l + 1]);
-    if (int rc = i2sdf_hip_check(hipGetLastError(), "mc_scan_reduce")) return rc;
-  }
-  mc_scan_chunks<<<1, MC_THREADS, 0, st>>>(lv[L.n_levels - 1], L.level_n[L.n_levels - 1], nullptr, total);
-  if (int rc = i2sdf_hip_check(hipGetLastError(), "mc_scan_chunks")) return rc;
-  for (int l = L.n_levels - 2; l >= 0; --l) {
-    mc_scan_chunks<<<(unsigned)L.level_n[l + 1], MC_THREADS, 0, st>>>(lv[l], L.level_n[l], lv[l + 1], nullptr);
-    if (int rc = i2sdf_hip_check(hipGetLastError(), "mc_scan_chunks")) return rc;
-  }
+  if (int rc = scan_levels_exclusive(ws, L.scan, total, st)) return rc;
   if (counts_out) return i2sdf_hip_check(hipMemcpyAsync(counts_out, total, 16, hipMemcpyDeviceToDevice, st), "marching cubes counts");
   return I2SDF_OK;
 }
@@ -304,7 +219,7 @@ extern "C" int i2sdf_marching_cubes_emit(const float* vol, int32_t nx, int32_t n
   const Vol V{vol, nx, ny, nz, (int64_t)ny * nz, nz, L.n, level};
   Geo G;
   for (int c = 0; c < 3; ++c) { G.sp[c] = spacing[c]; G.org[c] = origin[c]; }
-  const longlong2* blk = (const longlong2*)(ws + L.level_off[0]);
+  const longlong2* blk = (const longlong2*)(ws + L.scan.level_off[0]);
   int32_t* pofs = (int32_t*)(ws + L.off_pofs);
   uint8_t* pmask = (uint8_t*)(ws + L.off_mask);
   mc_emit_verts<<<(unsigned)L.nb0, MC_THREADS, 0, st>>>(V, G, blk, pofs, pmask, verts, normals, cap_v);

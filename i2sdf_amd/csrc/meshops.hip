@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/i2sdf.h"
+#include "blockops.h"
 
 // every product and sum rounded on its own, like the numpy restatement of the tests (no fused multiply-adds)
 #pragma clang fp contract(off)
@@ -24,10 +25,9 @@ int i2sdf_hip_check(hipError_t e, const char* what);
 
 namespace {
 
+using namespace i2sdf_blockops;
+
 constexpr int MO_THREADS = 256;
-constexpr int SCAN_ITEMS = 4;
-constexpr int SCAN_CHUNK = MO_THREADS * SCAN_ITEMS;    // items per scan workgroup
-constexpr int MAX_LEVELS = 8;
 
 #define RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 
@@ -120,34 +120,6 @@ __global__ __launch_bounds__(MO_THREADS) void mo_face_areas(const float* __restr
 }
 
 // ---------------------------------------------------------------------------------------------- fp64 running sum
-__device__ __forceinline__ double wave_incl(double x, int lane) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const double y = __shfl_up(x, d, 64);
-    if (lane >= d) x += y;
-  }
-  return x;
-}
-
-// exclusive prefix of x over the block's 256 threads (thread order); `total` = the block's sum
-__device__ double block_excl(double x, double& total) {
-  __shared__ double ws[MO_THREADS / 64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const double inc = wave_incl(x, lane);
-  if (lane == 63) ws[w] = inc;
-  __syncthreads();
-  double base = 0, tot = 0;
-#pragma unroll
-  for (int u = 0; u < MO_THREADS / 64; ++u) {
-    if (u < w) base += ws[u];
-    tot += ws[u];
-  }
-  __syncthreads();
-  total = tot;
-  const double left = __shfl_up(inc, 1, 64);       // the wave's inclusive sum one lane to the left = this lane's exclusive one
-  return lane ? base + left : base;
-}
-
 struct SrcF32 {                                    // level 0: x[order[i]] (order NULL: x[i]) widened to fp64
   const float* x; const int64_t* order; int64_t n_src;
   __device__ double operator()(int64_t i) const {
@@ -155,63 +127,11 @@ struct SrcF32 {                                    // level 0: x[order[i]] (orde
     return j >= 0 && j < n_src ? (double)x[j] : 0.0;
   }
 };
-struct SrcF64 {
-  const double* x;
-  __device__ double operator()(int64_t i) const { return x[i]; }
-};
 
-template <class Src>
-__global__ __launch_bounds__(MO_THREADS) void mo_scan_reduce(Src src, int64_t n, double* __restrict__ sums) {
-  const int64_t base = (int64_t)blockIdx.x * SCAN_CHUNK + threadIdx.x * SCAN_ITEMS;
-  double x = 0;
-#pragma unroll
-  for (int u = 0; u < SCAN_ITEMS; ++u)
-    if (base + u < n) x += src(base + u);
-  double tot;
-  (void)block_excl(x, tot);
-  if (threadIdx.x == 0) sums[blockIdx.x] = tot;
-}
-
-// out[chunk b] <- prefix within the chunk + add[b] (add NULL: 0); INCLUSIVE: item i included (the running sum), else excluded
-template <class Src, bool INCLUSIVE>
-__global__ __launch_bounds__(MO_THREADS) void mo_scan_chunks(Src src, int64_t n, const double* __restrict__ add, double* out) {
-  const int64_t base = (int64_t)blockIdx.x * SCAN_CHUNK + threadIdx.x * SCAN_ITEMS;
-  double it[SCAN_ITEMS];
-  double x = 0;
-#pragma unroll
-  for (int u = 0; u < SCAN_ITEMS; ++u) {
-    it[u] = base + u < n ? src(base + u) : 0.0;
-    x += it[u];
-  }
-  double tot;
-  double o = block_excl(x, tot);
-  if (add) o += add[blockIdx.x];
-#pragma unroll
-  for (int u = 0; u < SCAN_ITEMS; ++u) {
-    if (INCLUSIVE) o += it[u];
-    if (base + u < n) out[base + u] = o;
-    if (!INCLUSIVE) o += it[u];
-  }
-}
-
-struct ScanLayout {
-  int n_levels;                                    // levels of block sums above the items
-  int64_t level_off[MAX_LEVELS], level_n[MAX_LEVELS], bytes;
-};
-
-bool scan_layout(int64_t n, ScanLayout& L) {
-  if (n < 0 || n > INT32_MAX) return false;
-  L.n_levels = 0;
-  int64_t o = 0;
-  for (int64_t m = (n + SCAN_CHUNK - 1) / SCAN_CHUNK; m > 0; m = (m + SCAN_CHUNK - 1) / SCAN_CHUNK) {
-    if (L.n_levels == MAX_LEVELS) return false;
-    L.level_off[L.n_levels] = o;
-    L.level_n[L.n_levels] = m;
-    ++L.n_levels;
-    o += 8 * m;
-    if (m == 1) break;
-  }
-  L.bytes = o > 16 ? o : 16;
+// levels of chunk sums above the n items (blockops.h); at least 16 bytes, so that a caller's allocation is never empty
+bool scan_layout(int64_t n, ScanLevels& L) {
+  if (!fits(n) || !scan_levels((n + SCAN_CHUNK - 1) / SCAN_CHUNK, sizeof(double), 0, L)) return false;
+  if (L.bytes < 16) L.bytes = 16;
   return true;
 }
 
@@ -318,13 +238,10 @@ __global__ __launch_bounds__(MO_THREADS) void mo_sample(const float* __restrict_
   }
 }
 
-inline unsigned blocks(int64_t n) { return (unsigned)((n + MO_THREADS - 1) / MO_THREADS); }
-inline bool fits(int64_t n) { return n >= 0 && n <= INT32_MAX; }
-
 }  // namespace
 
 extern "C" int64_t i2sdf_mesh_scan_workspace_bytes(int64_t n) {
-  ScanLayout L;
+  ScanLevels L;
   return scan_layout(n, L) ? L.bytes : 0;
 }
 
@@ -341,7 +258,7 @@ extern "C" int i2sdf_mesh_edge_keys(const int32_t* faces, int64_t F, int64_t n_v
   if (!fits(F) || !fits(n_verts)) return I2SDF_EINVAL;
   if (F == 0) return I2SDF_OK;
   if (!faces || !keys || !status) return I2SDF_EINVAL;
-  mo_edge_keys<<<blocks(F), MO_THREADS, 0, (hipStream_t)stream>>>(faces, F, (int32_t)n_verts, keys, status);
+  mo_edge_keys<<<blocks(F, MO_THREADS), MO_THREADS, 0, (hipStream_t)stream>>>(faces, F, (int32_t)n_verts, keys, status);
   return i2sdf_hip_check(hipGetLastError(), "mo_edge_keys");
 }
 
@@ -350,11 +267,11 @@ extern "C" int i2sdf_mesh_face_components(const int64_t* sorted_keys, const int6
   if (F == 0) return I2SDF_OK;
   if (!sorted_keys || !perm || !labels) return I2SDF_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  mo_init_parent<<<blocks(F), MO_THREADS, 0, st>>>(labels, F);
+  mo_init_parent<<<blocks(F, MO_THREADS), MO_THREADS, 0, st>>>(labels, F);
   if (int rc = i2sdf_hip_check(hipGetLastError(), "mo_init_parent")) return rc;
-  mo_unite_runs<<<blocks(3 * F - 1), MO_THREADS, 0, st>>>(sorted_keys, perm, 3 * F, labels);
+  mo_unite_runs<<<blocks(3 * F - 1, MO_THREADS), MO_THREADS, 0, st>>>(sorted_keys, perm, 3 * F, labels);
   if (int rc = i2sdf_hip_check(hipGetLastError(), "mo_unite_runs")) return rc;
-  mo_flatten<<<blocks(F), MO_THREADS, 0, st>>>(labels, F);
+  mo_flatten<<<blocks(F, MO_THREADS), MO_THREADS, 0, st>>>(labels, F);
   return i2sdf_hip_check(hipGetLastError(), "mo_flatten");
 }
 
@@ -363,34 +280,24 @@ extern "C" int i2sdf_mesh_face_areas(const float* verts, int64_t n_verts, const 
   if (!fits(F) || !fits(n_verts)) return I2SDF_EINVAL;
   if (F == 0) return I2SDF_OK;
   if (!verts || !faces || !area || !status) return I2SDF_EINVAL;
-  mo_face_areas<<<blocks(F), MO_THREADS, 0, (hipStream_t)stream>>>(verts, (int32_t)n_verts, faces, F, area, status);
+  mo_face_areas<<<blocks(F, MO_THREADS), MO_THREADS, 0, (hipStream_t)stream>>>(verts, (int32_t)n_verts, faces, F, area, status);
   return i2sdf_hip_check(hipGetLastError(), "mo_face_areas");
 }
 
 extern "C" int i2sdf_mesh_cumsum_f64(const float* x, int64_t n_x, const int64_t* order, int64_t n, double* cdf, void* workspace, void* stream) {
-  ScanLayout L;
+  ScanLevels L;
   if (!fits(n_x) || !scan_layout(n, L) || (!order && n > n_x)) return I2SDF_EINVAL;
   if (n == 0) return I2SDF_OK;
   if (!x || !cdf || !workspace) return I2SDF_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  double* lv[MAX_LEVELS];
-  for (int l = 0; l < L.n_levels; ++l) lv[l] = (double*)((char*)workspace + L.level_off[l]);
+  double* sums = (double*)((char*)workspace + L.level_off[0]);
   const SrcF32 src{x, order, n_x};
-  // block sums up the levels, exclusive offsets down again, then the running sum of the items themselves
-  mo_scan_reduce<SrcF32><<<(unsigned)L.level_n[0], MO_THREADS, 0, st>>>(src, n, lv[0]);
-  if (int rc = i2sdf_hip_check(hipGetLastError(), "mo_scan_reduce")) return rc;
-  for (int l = 0; l + 1 < L.n_levels; ++l) {
-    mo_scan_reduce<SrcF64><<<(unsigned)L.level_n[l + 1], MO_THREADS, 0, st>>>(SrcF64{lv[l]}, L.level_n[l], lv[l + 1]);
-    if (int rc = i2sdf_hip_check(hipGetLastError(), "mo_scan_reduce")) return rc;
-  }
-  for (int l = L.n_levels - 1; l >= 0; --l) {
-    const bool top = l == L.n_levels - 1;
-    mo_scan_chunks<SrcF64, false><<<top ? 1u : (unsigned)L.level_n[l + 1], MO_THREADS, 0, st>>>(SrcF64{lv[l]}, L.level_n[l],
-                                                                                             top ? nullptr : lv[l + 1], lv[l]);
-    if (int rc = i2sdf_hip_check(hipGetLastError(), "mo_scan_chunks")) return rc;
-  }
-  mo_scan_chunks<SrcF32, true><<<(unsigned)L.level_n[0], MO_THREADS, 0, st>>>(src, n, lv[0], cdf);
-  return i2sdf_hip_check(hipGetLastError(), "mo_scan_chunks");
+  // chunk sums, their exclusive offsets (up the levels and down again), then the running sum of the items themselves
+  scan_reduce_kernel<SrcF32, double><<<(unsigned)L.level_n[0], SCAN_THREADS, 0, st>>>(src, n, sums);
+  if (int rc = i2sdf_hip_check(hipGetLastError(), "scan_reduce_kernel")) return rc;
+  if (int rc = scan_levels_exclusive<double>(workspace, L, nullptr, st)) return rc;
+  scan_chunks_kernel<SrcF32, double, true><<<(unsigned)L.level_n[0], SCAN_THREADS, 0, st>>>(src, n, sums, cdf, nullptr);
+  return i2sdf_hip_check(hipGetLastError(), "scan_chunks_kernel");
 }
 
 extern "C" int i2sdf_mesh_largest_label(const int32_t* sorted_labels, const double* cdf, int64_t F, int64_t* best, void* stream) {
@@ -400,9 +307,9 @@ extern "C" int i2sdf_mesh_largest_label(const int32_t* sorted_labels, const doub
   if (int rc = i2sdf_hip_check(hipGetLastError(), "mo_best_init")) return rc;
   if (F == 0) return I2SDF_OK;
   if (!sorted_labels || !cdf) return I2SDF_EINVAL;
-  mo_best_area<<<blocks(F), MO_THREADS, 0, st>>>(sorted_labels, cdf, F, (unsigned long long*)best);
+  mo_best_area<<<blocks(F, MO_THREADS), MO_THREADS, 0, st>>>(sorted_labels, cdf, F, (unsigned long long*)best);
   if (int rc = i2sdf_hip_check(hipGetLastError(), "mo_best_area")) return rc;
-  mo_best_label<<<blocks(F), MO_THREADS, 0, st>>>(sorted_labels, cdf, F, (unsigned long long*)best);
+  mo_best_label<<<blocks(F, MO_THREADS), MO_THREADS, 0, st>>>(sorted_labels, cdf, F, (unsigned long long*)best);
   return i2sdf_hip_check(hipGetLastError(), "mo_best_label");
 }
 
@@ -416,7 +323,7 @@ extern "C" int i2sdf_mesh_compact_mark(const int32_t* faces, const uint8_t* mask
   }
   if (F == 0) return I2SDF_OK;
   if (!faces || !mask || !fkeep || !status) return I2SDF_EINVAL;
-  mo_mark<<<blocks(F), MO_THREADS, 0, st>>>(faces, mask, F, (int32_t)n_verts, fkeep, vflag, status);
+  mo_mark<<<blocks(F, MO_THREADS), MO_THREADS, 0, st>>>(faces, mask, F, (int32_t)n_verts, fkeep, vflag, status);
   return i2sdf_hip_check(hipGetLastError(), "mo_mark");
 }
 
@@ -428,12 +335,12 @@ extern "C" int i2sdf_mesh_compact_gather(const float* verts, const float* normal
   hipStream_t st = (hipStream_t)stream;
   if (F > 0 && cap_f > 0) {
     if (!faces || !fkeep || !fscan || !vscan || !out_faces) return I2SDF_EINVAL;
-    mo_compact_faces<<<blocks(F), MO_THREADS, 0, st>>>(faces, fkeep, fscan, vscan, F, out_faces, cap_f);
+    mo_compact_faces<<<blocks(F, MO_THREADS), MO_THREADS, 0, st>>>(faces, fkeep, fscan, vscan, F, out_faces, cap_f);
     if (int rc = i2sdf_hip_check(hipGetLastError(), "mo_compact_faces")) return rc;
   }
   if (n_verts > 0 && cap_v > 0) {
     if (!verts || !vflag || !vscan || !out_verts) return I2SDF_EINVAL;
-    mo_compact_verts<<<blocks(n_verts), MO_THREADS, 0, st>>>(verts, normals, vflag, vscan, n_verts, out_verts, out_normals, cap_v);
+    mo_compact_verts<<<blocks(n_verts, MO_THREADS), MO_THREADS, 0, st>>>(verts, normals, vflag, vscan, n_verts, out_verts, out_normals, cap_v);
     if (int rc = i2sdf_hip_check(hipGetLastError(), "mo_compact_verts")) return rc;
   }
   return I2SDF_OK;
@@ -446,7 +353,7 @@ extern "C" int i2sdf_mesh_sample_surface(const float* verts, int64_t n_verts, co
   if (count == 0) return I2SDF_OK;
   if (F == 0) return I2SDF_EINVAL;                 // nothing to draw from
   if (!verts || !faces || !cdf || !u_face || !u_bary || !points || !face_index || !status) return I2SDF_EINVAL;
-  mo_sample<<<blocks(count), MO_THREADS, 0, (hipStream_t)stream>>>(verts, (int32_t)n_verts, faces, F, cdf, u_face, u_bary, count, points,
+  mo_sample<<<blocks(count, MO_THREADS), MO_THREADS, 0, (hipStream_t)stream>>>(verts, (int32_t)n_verts, faces, F, cdf, u_face, u_bary, count, points,
                                                                     face_index, status);
   return i2sdf_hip_check(hipGetLastError(), "mo_sample");
 }

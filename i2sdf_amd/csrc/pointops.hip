@@ -23,6 +23,7 @@
 #include <math.h>
 #include <stdint.h>
 #include "../../include/i2sdf.h"
+#include "blockops.h"
 
 // every product and sum rounded on its own, like the numpy restatement of the tests (no fused multiply-adds)
 #pragma clang fp contract(off)
@@ -30,6 +31,9 @@
 int i2sdf_hip_check(hipError_t e, const char* what);
 
 namespace {
+
+using i2sdf_blockops::block_sum;
+using i2sdf_blockops::fits;
 
 constexpr int PO_THREADS = 256;
 constexpr int PO_MAX_BLOCKS = 2048;                // grid-stride beyond that
@@ -316,20 +320,6 @@ __global__ __launch_bounds__(PO_THREADS) void po_nn_fallback(const float* __rest
 }
 
 // ---------------------------------------------------------------------------------------------- thresholded reduce
-// sum of the block's 256 values in a fixed tree (the same for every run); valid in thread 0
-__device__ double block_sum(double x) {
-  __shared__ double ws[PO_THREADS / 64];
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) x += __shfl_xor(x, d, 64);
-  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = x;
-  __syncthreads();
-  double t = 0.0;
-#pragma unroll
-  for (int u = 0; u < PO_THREADS / 64; ++u) t += ws[u];
-  __syncthreads();
-  return t;
-}
-
 __global__ __launch_bounds__(PO_THREADS) void po_reduce_chunks(const float* __restrict__ dist, int64_t n, double threshold,
                                                                double* __restrict__ part) {
   const int64_t base = (int64_t)blockIdx.x * RED_CHUNK;
@@ -343,24 +333,20 @@ __global__ __launch_bounds__(PO_THREADS) void po_reduce_chunks(const float* __re
       c += v < threshold ? 1.0 : 0.0;
     }
   }
-  s = block_sum(s);
-  c = block_sum(c);                                // (whole numbers below 2^53: exact in any order)
+  s = block_sum<PO_THREADS>(s);
+  c = block_sum<PO_THREADS>(c);                    // (whole numbers below 2^53: exact in any order)
   if (threadIdx.x == 0) { part[2 * blockIdx.x] = s; part[2 * blockIdx.x + 1] = c; }
 }
 
 __global__ __launch_bounds__(PO_THREADS) void po_reduce_final(const double* __restrict__ part, int64_t n_part, double* __restrict__ out) {
   double s = 0.0, c = 0.0;
   for (int64_t i = threadIdx.x; i < n_part; i += PO_THREADS) { s += part[2 * i]; c += part[2 * i + 1]; }
-  s = block_sum(s);
-  c = block_sum(c);
+  s = block_sum<PO_THREADS>(s);
+  c = block_sum<PO_THREADS>(c);
   if (threadIdx.x == 0) { out[0] = s; out[1] = c; }
 }
 
-inline unsigned blocks(int64_t n) {
-  const int64_t b = (n + PO_THREADS - 1) / PO_THREADS;
-  return (unsigned)(b < 1 ? 1 : (b > PO_MAX_BLOCKS ? PO_MAX_BLOCKS : b));
-}
-inline bool fits(int64_t n) { return n >= 0 && n <= INT32_MAX; }
+inline unsigned blocks(int64_t n) { return i2sdf_blockops::blocks(n, PO_THREADS, PO_MAX_BLOCKS); }      // every kernel here strides
 
 }  // namespace
 

@@ -30,6 +30,7 @@ namespace {
 
 using i2sdf_philox::U4;
 using i2sdf_philox::philox4x32_10;
+using i2sdf_philox::u01;
 using namespace i2sdf_brdf;
 typedef Dual<float> DF;
 
@@ -37,7 +38,26 @@ constexpr unsigned SHADE_STREAM = 8u;
 constexpr int THREADS = 256;
 constexpr float INV_PI = 0.31830988618379067154f;
 
-__device__ __forceinline__ float u01(unsigned x) { return (float)(x >> 8) * 5.9604644775390625e-8f; }   // [0, 1), 24 bits, as draws.hip
+// The three sums of g_radiance_scale over the workgroup: lanes -> wave (butterfly) -> workgroup (LDS, wave order).  Every thread calls
+// it; thread c < 3 gets component c.
+__device__ __forceinline__ float workgroup_sum3(float p0, float p1, float p2) {
+  __shared__ float ws[THREADS / 64][3];
+  float part[3] = {p0, p1, p2};
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) part[c] += __shfl_xor(part[c], off);
+  const int wv = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { ws[wv][0] = part[0]; ws[wv][1] = part[1]; ws[wv][2] = part[2]; }
+  __syncthreads();
+  float t = 0.f;
+  if (threadIdx.x < 3) {
+    t = ws[0][threadIdx.x];
+#pragma unroll
+    for (int w = 1; w < THREADS / 64; ++w) t += ws[w][threadIdx.x];
+  }
+  return t;
+}
 
 struct ShadeArgs {
   const float *x, *view, *normal, *Kd, *Ks, *rough;      // (bn, 3) each, rough (bn, 1)
@@ -139,7 +159,6 @@ __global__ __launch_bounds__(THREADS) void shade_reduce_kernel(ShadeArgs a) {
 
 // (132 registers: 3 waves per SIMD.  Bounded to 128 for a fourth wave it spills 12 bytes a lane, and no kernel here may use scratch.)
 __global__ __launch_bounds__(THREADS) void shade_backward_kernel(ShadeArgs a) {
-  __shared__ float wave_sum[THREADS / 64][3];
   const int G = 1 << a.lg;
   const int64_t slot = ((int64_t)blockIdx.x * THREADS + threadIdx.x) >> a.lg;
   const int sub = threadIdx.x & (G - 1);
@@ -210,43 +229,20 @@ __global__ __launch_bounds__(THREADS) void shade_backward_kernel(ShadeArgs a) {
     }
     a.grough[p] = acc[6];
   }
-  if (a.partial != nullptr) {      // g_radiance_scale: lanes -> wave (butterfly) -> workgroup (LDS, wave order) -> this workgroup's slot
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) part[c] += __shfl_xor(part[c], off);
-    const int wv = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { wave_sum[wv][0] = part[0]; wave_sum[wv][1] = part[1]; wave_sum[wv][2] = part[2]; }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-      float t = wave_sum[0][threadIdx.x];
-#pragma unroll
-      for (int w = 1; w < THREADS / 64; ++w) t += wave_sum[w][threadIdx.x];
-      a.partial[3 * (int64_t)blockIdx.x + threadIdx.x] = t;
-    }
+  if (a.partial != nullptr) {      // (uniform) g_radiance_scale: this workgroup's slot
+    const float t = workgroup_sum3(part[0], part[1], part[2]);
+    if (threadIdx.x < 3) a.partial[3 * (int64_t)blockIdx.x + threadIdx.x] = t;
   }
 }
 
 // second pass of g_radiance_scale: one workgroup, lane t takes slots t, t + 256, ..., then the same wave / workgroup order
 __global__ __launch_bounds__(THREADS) void shade_scale_sum_kernel(const float* partial, int64_t blocks, float* out) {
-  __shared__ float wave_sum[THREADS / 64][3];
   float part[3] = {0.f, 0.f, 0.f};
   for (int64_t b = threadIdx.x; b < blocks; b += THREADS)
 #pragma unroll
     for (int c = 0; c < 3; ++c) part[c] += partial[3 * b + c];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-    for (int c = 0; c < 3; ++c) part[c] += __shfl_xor(part[c], off);
-  const int wv = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { wave_sum[wv][0] = part[0]; wave_sum[wv][1] = part[1]; wave_sum[wv][2] = part[2]; }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    float t = wave_sum[0][threadIdx.x];
-#pragma unroll
-    for (int w = 1; w < THREADS / 64; ++w) t += wave_sum[w][threadIdx.x];
-    out[threadIdx.x] = t;
-  }
+  const float t = workgroup_sum3(part[0], part[1], part[2]);
+  if (threadIdx.x < 3) out[threadIdx.x] = t;
 }
 
 int refuse(const std::string& why) { return i2sdf_refuse(why.c_str()); }

@@ -45,12 +45,15 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include "../../include/i2sdf.h"
+#include "blockops.h"
 
 #pragma clang fp contract(off)
 
 int i2sdf_hip_check(hipError_t e, const char* what);
 
 namespace {
+
+using i2sdf_blockops::block_excl_scan;
 
 #include "mcubes_tables.inc"
 
@@ -247,33 +250,6 @@ __device__ int edge_mask(const Grid& G, const int32_t* __restrict__ slot, const 
   return m;
 }
 
-__device__ __forceinline__ int wave_incl(int x, int lane) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int y = __shfl_up(x, d, 64);
-    if (lane >= d) x += y;
-  }
-  return x;
-}
-
-// exclusive prefix of x over the workgroup's 256 threads; total = the workgroup's sum
-__device__ int block_excl(int x, int& total) {
-  __shared__ int ws[TS_THREADS / 64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int inc = wave_incl(x, lane);
-  if (lane == 63) ws[w] = inc;
-  __syncthreads();
-  int base = 0, tot = 0;
-#pragma unroll
-  for (int u = 0; u < TS_THREADS / 64; ++u) {
-    if (u < w) base += ws[u];
-    tot += ws[u];
-  }
-  __syncthreads();
-  total = tot;
-  return base + inc - x;
-}
-
 __global__ __launch_bounds__(TS_THREADS) void ts_count(Grid G, const int32_t* __restrict__ slot, const int32_t* __restrict__ unit_cell,
                                                        const float* __restrict__ tsdf, const int16_t* __restrict__ cellcase,
                                                        uint8_t* __restrict__ emask, int64_t* __restrict__ blk) {
@@ -285,8 +261,8 @@ __global__ __launch_bounds__(TS_THREADS) void ts_count(Grid G, const int32_t* __
   emask[self] = (uint8_t)m;
   const int cs = cellcase[self];
   int tv, tt;
-  (void)block_excl(__popc(m), tv);
-  (void)block_excl(cs >= 0 ? kMcNumTri[cs] : 0, tt);
+  (void)block_excl_scan<TS_THREADS>((int)__popc(m), tv);
+  (void)block_excl_scan<TS_THREADS>(cs >= 0 ? kMcNumTri[cs] : 0, tt);
   if (threadIdx.x == 0) { blk[2 * (int64_t)blockIdx.x] = tv; blk[2 * (int64_t)blockIdx.x + 1] = tt; }
 }
 
@@ -311,7 +287,7 @@ __global__ __launch_bounds__(TS_THREADS) void ts_emit_verts(Pin P, Grid G, const
   const int64_t self = (int64_t)s * 4096 + lin;
   const int m = emask[self];
   int tot;
-  int64_t off = block_excl(__popc(m), tot) + blk_excl[2 * (int64_t)blockIdx.x];
+  int64_t off = block_excl_scan<TS_THREADS>((int)__popc(m), tot) + blk_excl[2 * (int64_t)blockIdx.x];
   pofs[self] = (int32_t)off;
   if (!m) return;
   int c[3];
@@ -349,7 +325,7 @@ __global__ __launch_bounds__(TS_THREADS) void ts_emit_faces(Grid G, const int32_
   const int cs = cellcase[self];
   const int nt = cs >= 0 ? kMcNumTri[cs] : 0;
   int tot;
-  const int64_t off = block_excl(nt, tot) + blk_excl[2 * (int64_t)blockIdx.x + 1];
+  const int64_t off = block_excl_scan<TS_THREADS>(nt, tot) + blk_excl[2 * (int64_t)blockIdx.x + 1];
   if (!nt) return;
   int c[3];
   cell_coords(G, unit_cell[s], c);

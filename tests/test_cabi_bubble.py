@@ -109,7 +109,7 @@ def test_bubble_kernels_use_no_scratch(tmp_path):
     obj = os.path.join(OBJ, "bubble.o")
     if not os.path.exists(obj) or not all(os.path.exists(f"{LLVM}/{t}") for t in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf")):
         pytest.skip("no in-tree build (i2sdf_amd/lib/obj/bubble.o) or no LLVM binutils")
-    if os.path.getmtime(obj) < max(os.path.getmtime(os.path.join(CSRC, f)) for f in ("bubble.hip", "philox.h")):
+    if os.path.getmtime(obj) < max(os.path.getmtime(os.path.join(CSRC, f)) for f in ("bubble.hip", "philox.h", "blockops.h")):
         pytest.skip("in-tree object is older than the source: run __graft_entry__.build()")
     kernels = _kernels_of(obj, str(tmp_path))
     want = ("bubble_keys_kernel", "bubble_hist_kernel", "bubble_pick_kernel", "bubble_collect_kernel", "bubble_finish_kernel",

@@ -126,7 +126,7 @@ def test_kmeans_kernels_use_no_scratch(tmp_path):
     obj = os.path.join(OBJ, "kmeans.o")
     if not os.path.exists(obj) or not all(os.path.exists(f"{LLVM}/{t}") for t in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf")):
         pytest.skip("no in-tree build (i2sdf_amd/lib/obj/kmeans.o) or no LLVM binutils")
-    if os.path.getmtime(obj) < max(os.path.getmtime(os.path.join(CSRC, f)) for f in ("kmeans.hip", "philox.h")):
+    if os.path.getmtime(obj) < max(os.path.getmtime(os.path.join(CSRC, f)) for f in ("kmeans.hip", "philox.h", "blockops.h")):
         pytest.skip("in-tree object is older than the source: run __graft_entry__.build()")
     kernels = _kernels_of(obj, str(tmp_path))
     want = ("kmeans_pp_first_kernel", "kmeans_pp_round_kernel", "kmeans_pp_emit_kernel", "kmeans_range_kernel", "kmeans_assign_kernel",

@@ -339,6 +339,32 @@ def test_runs_are_bitwise_identical():
         assert torch.equal(x, y)
 
 
+@pytest.mark.parametrize("permuted", [False, True])
+@pytest.mark.parametrize("n", [1, 255, 256, 257, 1023, 1024, 1025, 1024 * 1024, 1024 * 1024 + 1])
+def test_cumsum_f64_at_the_scan_boundaries(n, permuted):
+    """i2sdf_mesh_cumsum_f64 around a wave, a workgroup, a chunk of 1024 items and the size at which the second level of chunk sums
+    appears.  The items are the integers 0..7 in fp32: every partial sum is a whole number far below 2^53, so the fp64 running sum
+    is exact in any order of additions and the result must equal numpy's bit for bit.  The workspace is the size the library asks
+    for, with a canary behind it."""
+    from i2sdf_amd import lib as L
+    lib = L.load()
+    rng = np.random.default_rng(1000 * n + permuted)
+    x = rng.integers(0, 8, n).astype(np.float32)
+    order = rng.permutation(n).astype(np.int64) if permuted else None
+    want = np.cumsum((x[order] if permuted else x).astype(np.float64))
+    size = int(lib.i2sdf_mesh_scan_workspace_bytes(n))
+    assert size > 0
+    ws = torch.full((size + 256,), 0xA5, dtype=torch.uint8, device="cuda")
+    cdf = torch.full((n + 8,), -1.0, dtype=torch.float64, device="cuda")
+    dx, dorder = _cuda(x), (_cuda(order) if permuted else None)
+    rc = lib.i2sdf_mesh_cumsum_f64(L.ptr(dx), n, L.ptr(dorder) if permuted else None, n, L.ptr(cdf), L.ptr(ws), L.stream_ptr())
+    assert rc == 0
+    got = cdf.cpu().numpy()
+    assert np.array_equal(got[:n].view(np.int64), want.view(np.int64))
+    assert (got[n:] == -1.0).all()                                  # nothing written behind the n sums
+    assert bool((ws[size:] == 0xA5).all()), "bytes behind i2sdf_mesh_scan_workspace_bytes(n) were written"
+
+
 def test_argument_errors():
     """A face index equal to n_verts is reported, not dereferenced.  The vertex buffer has slack rows behind n_verts, so that
     even a broken validation would read memory this test owns."""
