@@ -37,6 +37,9 @@ def __getattr__(name):
     if name in ("KMeans", "kmeans_pp_centroid"):
         from . import cluster
         return getattr(cluster, name)
+    if name in ("SphereTracer", "TraceResult", "TraceResultF"):
+        from . import trace
+        return getattr(trace, name)
     if name == "RenderEngine":
         from .engine import RenderEngine
         return RenderEngine

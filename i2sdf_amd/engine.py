@@ -604,6 +604,51 @@ class RenderEngine:
         self._last_sampler_ws = ws
         return z_out, z_eik, iters
 
+    def trace_rays(self, cam_loc, dirs, t_min=None, t_max=None, *, eps=1e-4, max_steps=64, step_scale=1.0, route="auto", return_f=False,
+                   workspace=None, out=None):
+        """Sphere-trace the zero level of the SDF along the rays cam_loc + t dirs (N, 3), t in [t_min, t_max] (include/i2sdf.h: i2sdf_trace_rays,
+        where the marching rule is written out).  The default interval is the renderer's own, [ray_sampler.near, 2 scene_bounding_sphere];
+        each bound is a number or an (N,) tensor.  route: "auto", "stepwise" or "fused" (refused where the plan has no fused kernel).
+        -> named tuple (t (N,) fp32, status (N,) int32 -- i2sdf_amd.trace.HIT / MISS / UNRESOLVED / INSIDE --, steps (N,) int32
+        [, f_trace (max_steps, N): row s = the sdf at step s + 1 of the rays that took it, NaN elsewhere]).  Only enqueues: no host read.
+        `workspace` (fp32, at least i2sdf_trace_workspace_floats(N) elements) and `out` (dict of preallocated t / status / steps / f_trace)
+        let a caller own the buffers (the tests put canaries around them; a given f_trace is not pre-filled)."""
+        from . import trace as T
+        cfg = T.check_trace_cfg(eps, max_steps, step_scale, route)
+        cam, dirs, t0, t1 = T.check_trace_rays(cam_loc, dirs, self.cfg.sampler.near if t_min is None else t_min,
+                                               2.0 * self.cfg.scene_bounding_sphere if t_max is None else t_max)
+        N, dev = cam.shape[0], cam.device
+        if dev.type != self.device.type or (self.device.index is not None and dev.index != self.device.index):
+            raise ValueError(f"trace_rays: the rays are on {dev}, the engine on {self.device}")
+        out = dict(out or {})
+        shapes = {"t": ((N,), torch.float32), "status": ((N,), torch.int32), "steps": ((N,), torch.int32), "f_trace": ((max_steps, N), torch.float32)}
+        for k, b in out.items():
+            if k not in shapes:
+                raise ValueError(f"trace_rays: out has no entry {k!r}")
+            shp, dt = shapes[k]
+            if not (isinstance(b, torch.Tensor) and tuple(b.shape) == shp and b.dtype == dt and b.device == dev and b.is_contiguous()):
+                raise ValueError(f"trace_rays: out[{k!r}] must be a contiguous {dt} tensor {shp} on {dev}")
+        t = out["t"] if "t" in out else torch.empty(N, dtype=torch.float32, device=dev)
+        status = out["status"] if "status" in out else torch.empty(N, dtype=torch.int32, device=dev)
+        steps = out["steps"] if "steps" in out else torch.empty(N, dtype=torch.int32, device=dev)
+        f_trace = None
+        if return_f:
+            f_trace = out["f_trace"] if "f_trace" in out else torch.full((max_steps, N), float("nan"), dtype=torch.float32, device=dev)
+        n_ws = int(self._lib.i2sdf_trace_workspace_floats(N))
+        if workspace is None:
+            ws = torch.empty(max(n_ws, 1), dtype=torch.float32, device=dev)
+        else:
+            ws = workspace
+            if not (ws.device == dev and ws.dtype == torch.float32 and ws.is_contiguous() and ws.numel() >= n_ws):
+                raise ValueError(f"trace_rays: workspace must be a contiguous fp32 tensor of at least {n_ws} elements on {dev}")
+        if N > 0:
+            L.check(self._lib.i2sdf_trace_rays(self._plan, self._pk(), C.byref(cfg), L.ptr(cam), L.ptr(dirs), L.ptr(t0), L.ptr(t1), N, L.ptr(t),
+                                               L.ptr(status), L.ptr(steps), L.ptr(f_trace), L.ptr(ws), L.stream_ptr()), "i2sdf_trace_rays", reason=True)
+        elif cfg.route == L.TRACE_ROUTES["fused"]:
+            L.check(self._lib.i2sdf_trace_rays(self._plan, None, C.byref(cfg), None, None, None, None, 0, None, None, None, None, None, None),
+                    "i2sdf_trace_rays", reason=True)      # (an empty batch is refused the fused route like any other)
+        return T.TraceResultF(t, status, steps, f_trace) if return_f else T.TraceResult(t, status, steps)
+
     def error_bound(self, z, sdf, beta, d_star=None, want_d_star=False):
         """ErrorBoundSampler.get_error_bound (ray_sampler.py:243-251) on rows z, sdf (B,n); beta scalar tensor or (B,) / (B,1).
         d_star=None computes the Theorem-1 bound (:99-114).  Returns bound (B,) [, d_star (B,n-1)]."""

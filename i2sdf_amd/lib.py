@@ -41,6 +41,10 @@ class Exchange(C.Structure):
     _fields_ = [("allreduce", EXCHANGE_FN), ("ctx", C.c_void_p)]
 
 
+class TraceCfg(C.Structure):
+    _fields_ = [("eps", C.c_float), ("step_scale", C.c_float), ("max_steps", C.c_int32), ("route", C.c_int32)]
+
+
 class LossCfg(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("eikonal_w", "smooth_w", "mask_w", "depth_w", "normal_w", "angular_w", "bubble_w", "light_w")] + \
                [("smooth_on", C.c_int32), ("reserved", C.c_int32), ("exchange", C.POINTER(Exchange))]
@@ -87,6 +91,9 @@ SSIM_TILE_X, SSIM_TILE_Y = 32, 16    # I2SDF_SSIM_TILE_X, I2SDF_SSIM_TILE_Y
 BUBBLE_MAX_K = 4096              # I2SDF_BUBBLE_MAX_K
 BUBBLE_WS_PASSES_OFFSET = 24     # I2SDF_BUBBLE_WS_PASSES_OFFSET
 KMEANS_MAX_K = 256               # I2SDF_KMEANS_MAX_K
+TRACE_HIT, TRACE_MISS, TRACE_UNRESOLVED, TRACE_INSIDE = 1, 2, 3, 4      # I2SDF_TRACE_*: status of a traced ray
+TRACE_ROUTES = {"auto": 0, "stepwise": 1, "fused": 2}                   # I2SDF_TRACE_AUTO / _STEPWISE / _FUSED
+TRACE_MAX_STEPS = 1024           # I2SDF_TRACE_MAX_STEPS
 
 
 class I2SDFError(RuntimeError):
@@ -255,6 +262,9 @@ SIGNATURES = {
     "i2sdf_kmeans_fit": (C.c_int, [_P, _I64, _I64, _P, _I32, _D, _P, _P, _P, _P]),
     # points, n, centroids, k, labels, dist2, stream
     "i2sdf_kmeans_assign": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _P]),
+    "i2sdf_trace_workspace_floats": (_I64, [_I64]),
+    # plan, packed, cfg, cam, dirs, t_min, t_max, N, t_out, status_out, steps_out, f_trace, workspace, stream
+    "i2sdf_trace_rays": (C.c_int, [_P, _P, C.POINTER(TraceCfg)] + [_P] * 4 + [_I64] + [_P] * 6),
     "i2sdf_light_forward": (C.c_int, [_P, _P, _P, _I64, _I64, _P, _P, _P]),
     "i2sdf_light_backward": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _P, _P, _P]),
     "i2sdf_loss_scratch_floats": (_I64, []),

@@ -546,10 +546,17 @@ class I2SDFNetwork(nn.Module):
         origin, as every camera ray is (the sampler intersects no sphere without a background network), so an origin outside the bounding
         sphere is not an error and not a special case: where the ray misses the scene the weights vanish and the radiance is ~0, the
         counterpart of the (0, 0) interval i2sdf_sphere_intersections gives a miss.
-        `intersect_func` (the reference's hook for an external ray caster) is not supported: anything but None is refused."""
+        `intersect_func` (the reference's hook for a ray caster): None, or a tracer of THIS module (`self.sphere_tracer(...)`,
+        i2sdf_amd.SphereTracer) -- the result is then `rgb_values` of `render_surface` for those rays: the radiance net at the first
+        surface hit, zero where the ray hits nothing, a few tens of SDF evaluations per ray instead of the sampler's several hundred.
+        Anything else -- a callable, a tracer bound to another module -- is refused: there is no external ray caster to call."""
         if intersect_func is not None:
-            raise NotImplementedError("get_incident_radiance: intersect_func is not supported (the secondary rays are rendered by the volume "
-                                      "renderer itself, there is no external ray caster to call)")
+            from .trace import SphereTracer, _rays_input
+            if isinstance(intersect_func, SphereTracer) and intersect_func.net is self:
+                return self.render_surface(_rays_input(pts, dirs, "get_incident_radiance"), **intersect_func.kw)["rgb_values"]
+            raise NotImplementedError("get_incident_radiance: intersect_func is not supported unless it is this module's own sphere_tracer() "
+                                      "(otherwise the secondary rays are rendered by the volume renderer itself, there is no external ray "
+                                      "caster to call)")
         if pts.dim() != 2 or pts.shape[1] != 3 or dirs.shape != pts.shape:
             raise ValueError(f"get_incident_radiance: pts {tuple(pts.shape)} and dirs {tuple(dirs.shape)} must both be (n, 3)")
         pts, dirs = pts.detach().to(torch.float32).contiguous(), dirs.detach().to(torch.float32).contiguous()
@@ -560,6 +567,107 @@ class I2SDFNetwork(nn.Module):
             return self.forward({"uv": pts, "rays": rays}, predict_only=True)["rgb_values"]
         finally:
             self.train(was_training)
+
+    # ------------------------------------------------------------------------------------------
+    # the surface itself: sphere tracing (include/i2sdf.h: i2sdf_trace_rays)
+    def sphere_tracer(self, **kw):
+        """An `intersect_func` bound to this module (i2sdf_amd.SphereTracer); kw: eps, max_steps, step_scale, route, t_min, t_max of
+        RenderEngine.trace_rays."""
+        from .trace import SphereTracer
+        return SphereTracer(self, **kw)
+
+    @staticmethod
+    def _surface_rays(input, who):
+        """(cam_loc, dirs, dnorm) of an `input` in the `rays` form, or None when they have to be set up from uv / pose / intrinsics"""
+        if not isinstance(input, dict) or "uv" not in input:
+            raise ValueError(f"{who}: input must be the dict forward takes (uv, pose, intrinsics) or its `rays` form (uv, rays)")
+        rays = input.get("rays")
+        if rays is None:
+            for k in ("pose", "intrinsics"):
+                if k not in input:
+                    raise ValueError(f"{who}: input has neither `rays` nor `{k}`")
+            uv = input["uv"]
+            if not isinstance(uv, torch.Tensor) or uv.dim() != 3 or uv.shape[2] != 2:
+                raise ValueError(f"{who}: uv {tuple(getattr(uv, 'shape', ()))} must be (batch, pixels, 2)")
+            return None
+        for k in ("cam_loc", "dirs", "dnorm"):
+            if k not in rays:
+                raise ValueError(f"{who}: input['rays'] has no `{k}`")
+        cam, dirs, dnorm = rays["cam_loc"], rays["dirs"], rays["dnorm"]
+        if cam.dim() != 2 or cam.shape[1] != 3 or dirs.shape != cam.shape or dnorm.numel() != cam.shape[0]:
+            raise ValueError(f"{who}: rays cam_loc {tuple(cam.shape)}, dirs {tuple(dirs.shape)}, dnorm {tuple(dnorm.shape)} must be (N, 3), (N, 3), (N,)")
+        if dirs.device != cam.device or dnorm.device != cam.device:
+            raise ValueError(f"{who}: rays on different devices ({cam.device}, {dirs.device}, {dnorm.device})")
+        return cam, dirs, dnorm.reshape(-1)
+
+    def _surface(self, input, with_rgb, split_n_pixels, who, kw):
+        from . import lib as L_
+        from .trace import check_trace_cfg
+        check_trace_cfg(**{k: v for k, v in kw.items() if k in ("eps", "max_steps", "step_scale", "route")})
+        if split_n_pixels is not None and (isinstance(split_n_pixels, bool) or not isinstance(split_n_pixels, int) or split_n_pixels < 1):
+            raise ValueError(f"{who}: split_n_pixels = {split_n_pixels!r} must be a positive integer or None")
+        rays = self._surface_rays(input, who)
+        eng = self._engine_for(input["uv"].device if rays is None else rays[0].device)
+        was_training = self.training
+        self.train(False)
+        try:
+            with torch.no_grad(), torch.cuda.device(eng.device):
+                if rays is None:
+                    cam, dirs, dnorm = eng.ray_setup(input["uv"], input["pose"], input["intrinsics"])
+                else:
+                    cam, dirs, dnorm = (t.detach().to(torch.float32).contiguous() for t in rays)
+                N, dev = cam.shape[0], cam.device
+                step = N if split_n_pixels is None else split_n_pixels
+                bounds = {k: kw[k] for k in ("t_min", "t_max") if k in kw}
+                tkw = {k: v for k, v in kw.items() if k not in ("t_min", "t_max")}
+                parts = []
+                for lo in range(0, max(N, 1), max(step, 1)):
+                    hi = min(lo + step, N)
+                    b = {k: (v[lo:hi] if isinstance(v, torch.Tensor) and v.dim() == 1 and v.shape[0] == N else v) for k, v in bounds.items()}
+                    c, d = cam[lo:hi], dirs[lo:hi]
+                    tr = eng.trace_rays(c, d, **b, **tkw)
+                    n = hi - lo
+                    hit = tr.status == L_.TRACE_HIT
+                    o = {"status": tr.status, "hit": hit, "t": tr.t, "depth_values": tr.t / dnorm[lo:hi]}
+                    zero3 = torch.zeros(n, 3, dtype=torch.float32, device=dev)
+                    if n == 0:
+                        o.update(points=zero3, normal_map=zero3, feature_vectors=torch.zeros(0, self.feature_vector_size, device=dev))
+                        if with_rgb:
+                            o["rgb_values"] = zero3
+                        parts.append(o)
+                        continue
+                    h3 = hit.unsqueeze(1)
+                    # value, gradient and features at the point where the march stopped
+                    fw = eng.sdf_forward_grad(rays=(c, d, tr.t.reshape(n, 1), 1), want_grad=True, save=False)
+                    # (fma(t, d, o) as the kernels form it, include/i2sdf.h: exact product and one rounding of the sum through fp64)
+                    o["points"] = torch.where(h3, (c.double() + tr.t.double().unsqueeze(1) * d.double()).float(), zero3)
+                    o["normal_map"] = torch.where(h3, torch.nn.functional.normalize(fw["grad"], dim=1), zero3)
+                    o["feature_vectors"] = torch.where(h3, fw["feat"][:n], torch.zeros((), dtype=torch.float32, device=dev))
+                    if with_rgb:
+                        rgb, _, _ = eng.rgb_forward(d, 1, fw["feat"], n, save=False, fw=fw)
+                        o["rgb_values"] = torch.where(h3, rgb, zero3)
+                    parts.append(o)
+                return parts[0] if len(parts) == 1 else {k: torch.cat([p_[k] for p_ in parts], 0) for k in parts[0]}
+        finally:
+            self.train(was_training)
+
+    def trace_surface(self, input, **kw):
+        """The first intersection of every ray of `input` with the zero level of the SDF, by sphere tracing (RenderEngine.trace_rays; kw are
+        its keywords: t_min, t_max, eps, max_steps, step_scale, route).  `input` is the dict `forward` takes, or its `rays` form
+        ({"uv": ..., "rays": {"cam_loc", "dirs", "dnorm"}}, as get_incident_radiance builds it).  Runs under no_grad whatever mode the
+        module is in (and leaves the mode as it was); nothing in here reads a result back.  Returns, per ray:
+          status (N,) int32 (i2sdf_amd.trace.HIT / MISS / UNRESOLVED / INSIDE), hit (N,) bool = status == HIT, t (N,) the depth along the
+          unit direction, depth_values (N,) = t / dnorm (the reference's depth convention), points (N, 3) = cam_loc + t dirs,
+          normal_map (N, 3) the normalised d sdf/dx there, feature_vectors (N, F).  points, normal_map and feature_vectors are exact zeros
+          on the rows without a hit; t is where the march stopped (t_max for a MISS)."""
+        return self._surface(input, False, None, "trace_surface", kw)
+
+    def render_surface(self, input, split_n_pixels=None, **kw):
+        """trace_surface plus rgb_values (N, 3): the radiance net at the hit -- in 'idr' mode on the hit point, the view direction and the
+        raw d sdf/dx, in 'nerf' mode on the view direction -- through the same forward entry points a render uses; zero without a hit.
+        A surface preview: a few tens of SDF evaluations and one radiance evaluation per pixel, no compositing.  split_n_pixels: rays per
+        chunk (None: one chunk); the chunks only bound the workspaces, the results do not depend on them."""
+        return self._surface(input, True, split_n_pixels, "render_surface", kw)
 
     def _extra_mask(self, dev):
         m = getattr(self, "_extra_mask_t", None)

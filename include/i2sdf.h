@@ -1135,6 +1135,63 @@ int i2sdf_kmeans_fit(const float* points, int64_t n, int64_t k, float* centroids
                      int64_t* labels, int32_t* n_iter, void* stream);
 int i2sdf_kmeans_assign(const float* points, int64_t n, const float* centroids, int64_t k, int64_t* labels, float* dist2, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Sphere tracing of the SDF's zero level -- the `intersect_func` hook of RenderingLayer.forward / get_incident_radiance
+ * (model/rendering/__init__.py, model/network/__init__.py).  The reference names the hook and released no implementation, so the
+ * marching rule is defined HERE; tests/trace_ref.py restates it in fp32 and fp64.  csrc/mlp_trace.hip, csrc/trace_rule.h.
+ * A march is a serial chain of network passes: its latency is steps x one sdf-only forward however few the rays.
+ *
+ * Per ray: origin o = cam[r], unit direction d = dirs[r], interval [t0, t1] = [t_min[r], t_max[r]].  State: t, lo, hi, bracketed, status,
+ * steps.  Every operation of the rule is ONE fp32 operation, rounded to nearest, in the order written, none contracted into an FMA
+ * (csrc/trace_rule.h switches contraction off for the rule).  The point of a depth t is the one the sdf-only forward forms from a ray,
+ * fetch_point of csrc/mlp_common.h: its `cam + t * dirs` is contracted by hipcc, so a component is fma(t, d, o), rounded ONCE -- the
+ * fused kernels form it from the same expression, and tests/test_gpu_trace.py holds every f to i2sdf_sdf_forward at that point bit for bit.
+ *   Init.  status = MISS if not (t1 > t0) (a NaN bound too); otherwise ACTIVE.  t = lo = hi = t0, bracketed = 0, steps = 0.
+ *   Step of an ACTIVE ray.  f = sdf(o + t d); steps += 1; then the FIRST of these that applies ends the step:
+ *     1. f not finite                      -> UNRESOLVED, t stays.
+ *     2. |f| <= eps                        -> HIT, t stays.
+ *     3. f < 0 and steps == 1              -> INSIDE (the origin lies behind the surface), t = t0.
+ *     4. f < 0: hi = t, bracketed = 1.  Otherwise lo = t.
+ *     5. bracketed:      tn = lo + 0.5f * (hi - lo);  tn == lo or tn == hi (the bracket is one fp32 step wide) -> HIT, t = hi.
+ *     6. not bracketed:  tn = t + step_scale * f;     tn >= t1 -> MISS, t = t1.
+ *     7. t = tn.
+ *   End.  A ray still ACTIVE after max_steps steps ends UNRESOLVED at its last t.
+ * The bracket (4, 5) is what makes an overshoot harmless: |grad sdf| of a fitted net exceeds 1 in places, a sphere-tracing step then
+ * lands behind the surface, and from there on the ray bisects between its last outside and its first inside depth.
+ *
+ *   cam, dirs (N,3) ; t_min, t_max (N) ; t_out (N) fp32 ; status_out, steps_out (N) int32
+ *   f_trace (max_steps, N) or NULL: row s holds the f of step s + 1 for the rays that took that step; other entries are left untouched.
+ *   workspace: i2sdf_trace_workspace_floats(N) floats (0 for N < 0), contents before the call do not matter.
+ * cfg.route:
+ *   I2SDF_TRACE_STEPWISE  per step one launch of the sdf-only forward of i2sdf_sdf_forward (three split planes under
+ *                         I2SDF_OPT_SDF_FWD_BF16X3, never the sampler's two) on the ray-form points, then one launch that applies the rule;
+ *                         finished rays are still evaluated.  Every plan has it.
+ *   I2SDF_TRACE_FUSED     one kernel: a workgroup keeps its 128 rays for the whole march -- per pass it forms the points, rebuilds the
+ *                         encoding, restarts the weight stream, runs the layer chain and applies the rule -- and leaves when none of its
+ *                         rays is ACTIVE (a tile of misses costs one or two passes).  Plans whose sdf-only forward runs in bf16x3 split
+ *                         arithmetic have one (I2SDF_OPT_SDF_FWD_BF16X3 on a 256/256 or 64/64 net); any other plan refuses this route.
+ *   I2SDF_TRACE_AUTO      the fused kernel where the plan has one, the stepwise route otherwise.  Measured on the synthetic.yml net
+ *                         (profiles/trace_timing.json): 37.0 against 79.5 ms at 307 200 rays, 6.5 against 6.8 ms at 1024.
+ *   All launches are stream ordered; the host reads nothing back; t, status, steps and f_trace do not depend on the route, bit for bit.
+ * Refused with I2SDF_EINVAL and a text in i2sdf_last_hip_error(), nothing launched: eps <= 0 or not finite; step_scale outside (0, 1];
+ *   max_steps outside 1..I2SDF_TRACE_MAX_STEPS; an unknown route; I2SDF_TRACE_FUSED on a plan without a fused kernel; a NULL pointer
+ *   (f_trace and stream excepted); N < 0 or N >= 2^31.  N = 0 succeeds and launches nothing.
+ * ---------------------------------------------------------------------------------------------- */
+#define I2SDF_TRACE_ACTIVE 0          /* only inside the march: never returned */
+#define I2SDF_TRACE_HIT 1
+#define I2SDF_TRACE_MISS 2
+#define I2SDF_TRACE_UNRESOLVED 3
+#define I2SDF_TRACE_INSIDE 4
+#define I2SDF_TRACE_AUTO 0
+#define I2SDF_TRACE_STEPWISE 1
+#define I2SDF_TRACE_FUSED 2
+#define I2SDF_TRACE_MAX_STEPS 1024
+typedef struct i2sdf_trace_cfg { float eps, step_scale; int32_t max_steps, route; } i2sdf_trace_cfg;
+int64_t i2sdf_trace_workspace_floats(int64_t N);
+int i2sdf_trace_rays(const i2sdf_plan* plan, const float* packed, const i2sdf_trace_cfg* cfg, const float* cam, const float* dirs,
+                     const float* t_min, const float* t_max, int64_t N, float* t_out, int32_t* status_out, int32_t* steps_out,
+                     float* f_trace, float* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
