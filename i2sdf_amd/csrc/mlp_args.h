@@ -80,6 +80,17 @@ struct RgbBwdArgs {
   int act = 0;              // output activation I2SDF_RGB_ACT_* of the forward (mlp_common.h: rgb_out_act_grad), wave uniform
 };
 
+// What decides the kernel of a radiance launch: the width (256 / 64), bf16x3 split arithmetic (256 wide only), the mode, the run-time view
+// embedder (0 = positional) and, in 'idr' mode, whether the view directions go through PE4.  false: the plan's shape has no radiance kernels
+struct RgbPath { bool wide, x3, idr, enc; int emb; };
+inline bool rgb_path(const i2sdf_plan* p, RgbPath* k) {
+  const i2sdf_mlp_desc& d = p->rgb.d;
+  const bool wide = d.hidden == 256 && p->F == 256;
+  if (!wide && !(d.hidden == 64 && p->F == 64)) return false;
+  *k = RgbPath{wide, wide && p->rgb_bf16x3 != 0, i2sdf::rgb_idr(d), d.multires == 4, i2sdf::rgb_embed(d)};
+  return true;
+}
+
 // bf16x3 kernels: launch over `grid` workgroups of 128 points -- four 32-point waves (mlp_x3.hip: d sdf/dx chain, sweeps) or eight 16-point
 // waves (mlp_x3h.hip: forward with saves, radiance net)
 void i2sdf_launch_igrad3(const SdfTrainFwdArgs& a, unsigned grid, hipStream_t st);
@@ -99,3 +110,12 @@ struct LightFwd3hArgs {
   float* hl;                            // (Mp, HL) point-major, or nullptr
 };
 void i2sdf_launch_light_fwd3h(const LightFwd3hArgs& a, unsigned grid, hipStream_t st);
+// bf16x3 sdf-only forwards: mlp_x3.hip (64-wide nets, 32-point waves), mlp_x3h.hip (256-wide, 16-point waves; `planes` = 3, or the sampler's 2)
+void i2sdf_launch_sdf_fwd3(int H, const float* stream, int n_stages, int L, int skip, const i2sdf::PointSpec& ps, const int* skip_flag, int64_t M,
+                           float* sdf_out, unsigned grid, hipStream_t st);
+void i2sdf_launch_sdf_fwd3h(const float* stream, int n_stages, int L, int skip, const i2sdf::PointSpec& ps, const int* skip_flag, int64_t M,
+                            float* sdf_out, int planes, hipStream_t st);
+// mlp_fwd.hip, internal (sampler, sphere tracing): i2sdf_sdf_forward at x = cam[r] + z[r*ldz + j]*dirs[r], j < n_per_ray; a no-op when *skip_flag != 0.
+// sampler_pass: the pass only chooses depths (two split planes under I2SDF_OPT_SAMPLER_BF16X2); false: the three planes of the public forward
+int i2sdf_sdf_forward_rays_flagged(const i2sdf_plan* p, const float* packed, const float* cam, const float* dirs, const float* z, int64_t ldz,
+                                   int32_t n_per_ray, int64_t B, float* sdf_out, const int* skip_flag, bool sampler_pass, void* stream);

@@ -10,9 +10,6 @@
 
 using namespace i2sdf;
 
-int i2sdf_hip_check(hipError_t e, const char* what);
-
-
 namespace {
 
 template <int H, int F, int LF>
@@ -381,24 +378,23 @@ extern "C" int i2sdf_sdf_backward(const i2sdf_plan* p, const float* packed, cons
   if (p->H == 256 && p->F == 256) {
     // full workgroups in bf16x3 split arithmetic (two launches); needs at least one plain hidden layer above the skip layer
     const bool x3 = p->sdf_bwd_bf16x3 != 0 && d.n_lin >= 4 && d.skip_layer != d.n_lin - 2;
-    SdfBwdArgs a3 = a;
-    if (x3) {
-      const Span fwd3 = span(p, packed, p->sdf, SPAN_FWD3_HIDDEN), rev3 = span(p, packed, p->sdf, SPAN_REV3_SWEEP2);
-      if (!fwd3.n_stages || !rev3.n_stages) return I2SDF_EINVAL;
-      a3.fwd = fwd3.w; a3.n_fwd = fwd3.n_stages; a3.rev = rev3.w; a3.n_rev = rev3.n_stages;
-      a3.kcs = sdf_blocked_points(p, M, Mp) > 0 ? KCS_BLK : KCS_PM;
-      a3.p24 = (sdf_saves24(p) && a3.kcs == KCS_BLK) ? 1 : 0;
-    }
+    const Span fwd3 = x3 ? span(p, packed, p->sdf, SPAN_FWD3_HIDDEN) : Span{}, rev3 = x3 ? span(p, packed, p->sdf, SPAN_REV3_SWEEP2) : Span{};
+    if (x3 && (!fwd3.n_stages || !rev3.n_stages)) return I2SDF_EINVAL;
+    const int kcs3 = sdf_blocked_points(p, M, Mp) > 0 ? KCS_BLK : KCS_PM;
     const bool ranged = x3 && i2sdf_parts_on(p);      // point ranges (plan.h: PartRun): both sweeps of a range on the range's stream
     ChainGuard guard(p, st, ranged);
     auto tail = [&](hipStream_t s, int64_t m0) {       // the partial last round as split-K workgroups (ksplit.h)
       launch_lds_bytes(KS_LDS_BYTES, sdf_bwd_split_kernel<256, 256, 6>, (unsigned)((M - m0 + 31) / 32), s, a, m0);
     };
     auto full = [&](hipStream_t s, int wg0, unsigned g, int64_t Mv) {
-      SdfBwdArgs x = x3 ? a3 : a;
+      SdfBwdArgs x = a;
       x.wg0 = wg0; x.M = Mv;
-      if (x3) i2sdf_launch_sdf_bwd3(x, g, s);
-      else launch_lds(sdf_bwd_kernel<256, 256, 6>, g, s, x);
+      if (x3) {
+        // what the bf16x3 launches take: their spans, the layout of the saved tensors (the fp32 and split-K launches: the fp32 spans, KCS_PM)
+        x.fwd = fwd3.w; x.n_fwd = fwd3.n_stages; x.rev = rev3.w; x.n_rev = rev3.n_stages;
+        x.kcs = kcs3; x.p24 = (sdf_saves24(p) && kcs3 == KCS_BLK) ? 1 : 0;
+        i2sdf_launch_sdf_bwd3(x, g, s);
+      } else launch_lds(sdf_bwd_kernel<256, 256, 6>, g, s, x);
     };
     i2sdf_dispatch_points(p, st, M, ranged, true, TAIL_FORKED, full, tail);
   } else if (p->H == 64 && p->F == 64) {
@@ -407,74 +403,70 @@ extern "C" int i2sdf_sdf_backward(const i2sdf_plan* p, const float* packed, cons
   return i2sdf_hip_check(hipGetLastError(), "sdf_backward launch");
 }
 
+namespace {
+
+// THE kernel choice of the radiance backward (the embedder and the view encoding do not reach it: nothing is differentiated through them).
+// tail_m0 < 0: `g` full workgroups from x.wg0 on; tail_m0 >= 0: the split-K form of the fp32 256-wide 'nerf' kernel over the points from tail_m0 on
+void launch_rgb_bwd(const RgbPath& k, const RgbBwdArgs& x, unsigned g, hipStream_t s, int64_t tail_m0 = -1) {
+  if (!k.idr && k.wide && (!k.x3 || tail_m0 >= 0)) {
+    if (tail_m0 < 0) launch_lds(rgb_bwd_kernel<256, 256>, g, s, x);
+    else launch_lds_bytes(KS_LDS_BYTES, rgb_bwd_split_kernel<256, 256>, g, s, x, tail_m0);
+  } else if (k.x3) {                       // 16-point waves (x3h.h)
+    if (k.idr) i2sdf_launch_rgb_bwd3h_idr(x, g, s);
+    else i2sdf_launch_rgb_bwd3h(x, g, s);
+  } else if (!k.idr) launch_lds(rgb_bwd_kernel<64, 64>, g, s, x);
+  else if (k.wide) launch_lds(rgb_bwd_kernel<256, 256, true>, g, s, x);
+  else launch_lds(rgb_bwd_kernel<64, 64, true>, g, s, x);
+}
+
+// The radiance backward of either mode behind the entry point's own checks; `a` holds the caller's arguments.  Launch shapes as rgb_forward
+// (mlp_train.hip): 'idr' runs full workgroups only.
+int rgb_backward(const i2sdf_plan* p, const float* packed, RgbBwdArgs a, hipStream_t st, const char* what) {
+  const i2sdf_mlp_desc& d = p->rgb.d;
+  RgbPath k;
+  if (!rgb_path(p, &k)) return I2SDF_EINVAL;
+  const bool may_split = k.wide && !k.idr;
+  Span rev, rev3;
+  if (!k.x3 || may_split) { rev = span(p, packed, p->rgb, SPAN_REV); if (!rev.n_stages) return I2SDF_EINVAL; }
+  if (k.x3) { rev3 = span(p, packed, p->rgb, SPAN_REV3H); if (!rev3.n_stages) return I2SDF_EINVAL; }
+  a.rev = rev.w; a.n_rev = rev.n_stages; a.L = d.n_lin; a.act = rgb_act(d);
+  const int kcs3 = rgb_blocked_points(p, a.M, a.Mp) > 0 ? KCS_BLK : KCS_PM;
+  const bool ranged = k.x3 && i2sdf_parts_on(p);
+  ChainGuard guard(p, st, ranged);
+  auto full = [&](hipStream_t s, int wg0, unsigned g, int64_t Mv) {
+    RgbBwdArgs x = a;
+    x.wg0 = wg0; x.M = Mv;
+    if (k.x3) { x.rev = rev3.w; x.n_rev = rev3.n_stages; x.kcs = kcs3; }      // what the bf16x3 launches take (the others: the fp32 span, KCS_PM)
+    launch_rgb_bwd(k, x, g, s);
+  };
+  auto tail = [&](hipStream_t s, int64_t m0) { launch_rgb_bwd(k, a, (unsigned)((a.M - m0 + 31) / 32), s, m0); };
+  i2sdf_dispatch_points(p, st, a.M, ranged, may_split, TAIL_BEHIND, full, tail);
+  return i2sdf_hip_check(hipGetLastError(), what);
+}
+
+}  // namespace
+
 extern "C" int i2sdf_rgb_backward(const i2sdf_plan* p, const float* packed, const float* rgb, const float* rgb_bar, const float* rs,
                                   int64_t M, int64_t Mp, float* gar, float* ga_last, float* fbar, void* stream) {
   if (M == 0) return I2SDF_OK;                 // empty batch: nothing to validate, nothing to launch
   if (!p || !packed || !rgb || !rgb_bar || !rs || !gar || !ga_last || !fbar || M < 0) return I2SDF_EINVAL;
   if (Mp < M || Mp % PTS_PER_WG) return I2SDF_EINVAL;
-  const i2sdf_mlp_desc& d = p->rgb.d;
-  if (rgb_idr(d)) return I2SDF_EINVAL;                  // ('idr' plans: i2sdf_rgb_backward_idr)
-  const bool wide = d.hidden == 256 && p->F == 256, x3 = wide && p->rgb_bf16x3;
-  if (!wide && !(d.hidden == 64 && p->F == 64)) return I2SDF_EINVAL;
-  const Span rev = span(p, packed, p->rgb, SPAN_REV);
-  if (!rev.n_stages) return I2SDF_EINVAL;
+  if (rgb_idr(p->rgb.d)) return I2SDF_EINVAL;           // ('idr' plans: i2sdf_rgb_backward_idr)
   RgbBwdArgs a{};
-  a.rev = rev.w; a.n_rev = rev.n_stages;
-  a.L = d.n_lin; a.M = M; a.Mp = Mp; a.rgb = rgb; a.rgb_bar = rgb_bar; a.rs = rs; a.gar = gar; a.ga_last = ga_last; a.fbar = fbar;
-  a.act = rgb_act(d);
-  RgbBwdArgs a3 = a;
-  if (x3) {                                           // 16-point waves (x3h.h)
-    const Span rev3 = span(p, packed, p->rgb, SPAN_REV3H);
-    if (!rev3.n_stages) return I2SDF_EINVAL;
-    a3.rev = rev3.w; a3.n_rev = rev3.n_stages;
-    a3.kcs = rgb_blocked_points(p, M, Mp) > 0 ? KCS_BLK : KCS_PM;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const bool ranged = x3 && i2sdf_parts_on(p);
-  ChainGuard guard(p, st, ranged);
-  auto full = [&](hipStream_t s, int wg0, unsigned g, int64_t Mv) {
-    RgbBwdArgs x = x3 ? a3 : a;
-    x.wg0 = wg0; x.M = Mv;
-    if (x3) i2sdf_launch_rgb_bwd3h(x, g, s);
-    else launch_lds(rgb_bwd_kernel<256, 256>, g, s, x);
-  };
-  auto tail = [&](hipStream_t s, int64_t m0) {
-    launch_lds_bytes(KS_LDS_BYTES, rgb_bwd_split_kernel<256, 256>, (unsigned)((M - m0 + 31) / 32), s, a, m0);
-  };
-  if (wide) i2sdf_dispatch_points(p, st, M, ranged, true, TAIL_BEHIND, full, tail);
-  else launch_lds(rgb_bwd_kernel<64, 64>, (unsigned)((M + PTS_PER_WG - 1) / PTS_PER_WG), st, a);
-  return i2sdf_hip_check(hipGetLastError(), "rgb_backward launch");
+  a.M = M; a.Mp = Mp; a.rgb = rgb; a.rgb_bar = rgb_bar; a.rs = rs; a.gar = gar; a.ga_last = ga_last; a.fbar = fbar;
+  return rgb_backward(p, packed, a, (hipStream_t)stream, "rgb_backward launch");
 }
 
-// 'idr' mode (include/i2sdf.h): the same launches over the kernels' IDR instantiations, full workgroups only (as i2sdf_rgb_forward_idr)
+// 'idr' mode (include/i2sdf.h): the same launches over the kernels' IDR instantiations
 extern "C" int i2sdf_rgb_backward_idr(const i2sdf_plan* p, const float* packed, const float* rgb, const float* rgb_bar, const float* rs,
                                       int64_t M, int64_t Mp, float* gar, float* ga_last, float* fbar, float* nbar, int32_t accumulate,
                                       void* stream) {
   if (M == 0) return I2SDF_OK;                 // empty batch: nothing to validate, nothing to launch
   if (!p || !packed || !rgb || !rgb_bar || !rs || !gar || !ga_last || !fbar || !nbar || M < 0) return I2SDF_EINVAL;
   if (Mp < M || Mp % PTS_PER_WG) return I2SDF_EINVAL;
-  const i2sdf_mlp_desc& d = p->rgb.d;
-  if (!rgb_idr(d)) return I2SDF_EINVAL;
-  const bool wide = d.hidden == 256 && p->F == 256, x3 = wide && p->rgb_bf16x3;
-  if (!wide && !(d.hidden == 64 && p->F == 64)) return I2SDF_EINVAL;
-  const Span rev = span(p, packed, p->rgb, x3 ? SPAN_REV3H : SPAN_REV);
-  if (!rev.n_stages) return I2SDF_EINVAL;
+  if (!rgb_idr(p->rgb.d)) return I2SDF_EINVAL;
   RgbBwdArgs a{};
-  a.rev = rev.w; a.n_rev = rev.n_stages;
-  a.L = d.n_lin; a.M = M; a.Mp = Mp; a.rgb = rgb; a.rgb_bar = rgb_bar; a.rs = rs; a.gar = gar; a.ga_last = ga_last; a.fbar = fbar;
-  a.act = rgb_act(d);
+  a.M = M; a.Mp = Mp; a.rgb = rgb; a.rgb_bar = rgb_bar; a.rs = rs; a.gar = gar; a.ga_last = ga_last; a.fbar = fbar;
   a.nbar = nbar; a.nbar_acc = accumulate ? 1 : 0;
-  if (x3) a.kcs = rgb_blocked_points(p, M, Mp) > 0 ? KCS_BLK : KCS_PM;
-  hipStream_t st = (hipStream_t)stream;
-  const bool ranged = x3 && i2sdf_parts_on(p);
-  ChainGuard guard(p, st, ranged);
-  auto full = [&](hipStream_t s, int wg0, unsigned g, int64_t Mv) {
-    RgbBwdArgs x = a;
-    x.wg0 = wg0; x.M = Mv;
-    if (x3) i2sdf_launch_rgb_bwd3h_idr(x, g, s);
-    else if (wide) launch_lds(rgb_bwd_kernel<256, 256, true>, g, s, x);
-    else launch_lds(rgb_bwd_kernel<64, 64, true>, g, s, x);
-  };
-  i2sdf_dispatch_points(p, st, M, ranged, false, TAIL_BEHIND, full, [](hipStream_t, int64_t) {});
-  return i2sdf_hip_check(hipGetLastError(), "rgb_backward_idr launch");
+  return rgb_backward(p, packed, a, (hipStream_t)stream, "rgb_backward_idr launch");
 }

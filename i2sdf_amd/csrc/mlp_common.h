@@ -7,36 +7,28 @@
 
 namespace i2sdf {
 
-// launch a 256-thread kernel with the double-buffered weight stage in dynamic LDS (> 64 KB needs the attribute once)
+// launch a kernel with `lds_bytes` of dynamic LDS (> 64 KB needs the attribute: set once per kernel)
 template <class K, class... A>
-inline void launch_lds_bytes(int lds_bytes, K kern, unsigned grid, hipStream_t st, A... args) {
+inline void launch_dyn_lds(int threads, int lds_bytes, K kern, dim3 grid, hipStream_t st, A... args) {
   static std::mutex mu;
   static std::unordered_set<const void*> done;
-  {
+  if (lds_bytes > 0) {
     std::lock_guard<std::mutex> lk(mu);
     if (!done.count((const void*)kern)) {
       (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
       done.insert((const void*)kern);
     }
   }
-  kern<<<grid, 256, lds_bytes, st>>>(args...);
+  kern<<<grid, threads, lds_bytes, st>>>(args...);
 }
+// a 256-thread kernel with the double-buffered weight stage in dynamic LDS
+template <class K, class... A>
+inline void launch_lds_bytes(int lds_bytes, K kern, unsigned grid, hipStream_t st, A... args) { launch_dyn_lds(256, lds_bytes, kern, grid, st, args...); }
 template <class K, class... A>
 inline void launch_lds(K kern, unsigned grid, hipStream_t st, A... args) { launch_lds_bytes(LDS_BYTES, kern, grid, st, args...); }
 // the same for a kernel of `threads` threads per workgroup (16-point-wave kernels, x3h.h: 512 = 8 waves, 256 = 4 waves)
 template <class K, class... A>
-inline void launch_lds_threads(int threads, K kern, unsigned grid, hipStream_t st, A... args) {
-  static std::mutex mu;
-  static std::unordered_set<const void*> done;
-  {
-    std::lock_guard<std::mutex> lk(mu);
-    if (!done.count((const void*)kern)) {
-      (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES_H);
-      done.insert((const void*)kern);
-    }
-  }
-  kern<<<grid, threads, LDS_BYTES_H, st>>>(args...);
-}
+inline void launch_lds_threads(int threads, K kern, unsigned grid, hipStream_t st, A... args) { launch_dyn_lds(threads, LDS_BYTES_H, kern, grid, st, args...); }
 
 // ---- layouts of the saved per-point tensors of width 256 (hs, abars, gus, gas; rs, gar) ------------------------------
 //   point-major  [Mp][256]                          row of point m at m*256, k-chunk kc (16 floats) at +16*kc
@@ -74,6 +66,16 @@ inline int64_t rgb_blocked_points(const i2sdf_plan* p, int64_t M, int64_t Mp) {
   if (i2sdf_parts_on(p) || i2sdf::rgb_idr(p->rgb.d)) return Mp;      // ('idr' mode: no split-K tail either, i2sdf_rgb_forward_idr)
   const int64_t bulk = split_bulk_points(M, p->n_cu);
   return bulk > 0 ? bulk : Mp;
+}
+
+// which kernel evaluates the sdf-only forward of a plan (mlp_fwd.hip: launch_sdf_fwd; the fused tracers of mlp_trace.hip follow the bf16x3 ones)
+enum SdfFwdKind { SDF_FWD_NONE, SDF_FWD_FP32, SDF_FWD_X3_64 /* 32-point waves, mlp_x3.hip */, SDF_FWD_X3H_256 /* 16-point waves, mlp_x3h.hip */ };
+inline SdfFwdKind sdf_fwd_kind(const i2sdf_plan* p) {
+  const bool wide = p->H == 256 && p->F == 256, slim = p->H == 64 && p->F == 64;
+  if (p->sdf.d.multires != 6 || (!wide && !slim)) return SDF_FWD_NONE;
+  if (p->sdf_fwd_bf16x3 && wide && span_chunks(p->sdf, SPAN_FWD3H) > 0) return SDF_FWD_X3H_256;
+  if (p->sdf_fwd_bf16x3 && slim && span_chunks(p->sdf, SPAN_FWD3) > 0) return SDF_FWD_X3_64;
+  return SDF_FWD_FP32;
 }
 
 constexpr float RS2 = 0.70710678118654752440f;

@@ -5,14 +5,6 @@
 
 using namespace i2sdf;
 
-int i2sdf_hip_check(hipError_t e, const char* what);
-// bf16x3 variant of the sdf-only forward: sdf_fwd3_kernel lives in mlp_x3.hip (the translation unit with the lifted unroll cap)
-void i2sdf_launch_sdf_fwd3(int H, const float* stream, int n_stages, int L, int skip, const PointSpec& ps, const int* skip_flag, int64_t M,
-                           float* sdf_out, unsigned grid, hipStream_t st);
-
-void i2sdf_launch_sdf_fwd3h(const float* stream, int n_stages, int L, int skip, const PointSpec& ps, const int* skip_flag, int64_t M, float* sdf_out,
-                            int planes, hipStream_t st);
-
 namespace {
 
 template <int H, int F, int LF, bool FULL>
@@ -72,21 +64,22 @@ int launch_sdf_fwd(const i2sdf_plan* p, const float* packed, PointSpec points, c
   const i2sdf_mlp_desc& d = p->sdf.d;
   const bool full = feat_out != nullptr;
   const unsigned grid = (unsigned)((M + PTS_PER_WG - 1) / PTS_PER_WG);
-  if (!full && sdf_out != nullptr && p->sdf_fwd_bf16x3 && H == 256 && span_chunks(p->sdf, SPAN_FWD3H) > 0) {
-    // 256-wide nets: 16-point waves, two per SIMD (x3h.h); the sampler's passes with two split planes under I2SDF_OPT_SAMPLER_BF16X2
+  const SdfFwdKind kind = sdf_fwd_kind(p);
+  if (!full && sdf_out != nullptr && kind == SDF_FWD_X3H_256) {
+    // the sampler's passes with two split planes under I2SDF_OPT_SAMPLER_BF16X2
     const int PL = (sampler_pass && p->sampler_bf16x2 && span_chunks(p->sdf, SPAN_FWD2H) > 0) ? 2 : 3;
     const Span s3 = span(p, packed, p->sdf, PL == 2 ? SPAN_FWD2H : SPAN_FWD3H_SDF);
     if (!s3.n_stages) return I2SDF_EINVAL;
     i2sdf_launch_sdf_fwd3h(s3.w, s3.n_stages, d.n_lin, d.skip_layer, points, skip_flag, M, sdf_out, PL, st);
     return i2sdf_hip_check(hipGetLastError(), "sdf_forward (bf16x3, 16-point waves) launch");
   }
-  if (!full && sdf_out != nullptr && p->sdf_fwd_bf16x3 && H == 64 && span_chunks(p->sdf, SPAN_FWD3) > 0) {
+  if (!full && sdf_out != nullptr && kind == SDF_FWD_X3_64) {
     const Span s3 = span(p, packed, p->sdf, SPAN_FWD3);
     if (!s3.n_stages) return I2SDF_EINVAL;
     i2sdf_launch_sdf_fwd3(H, s3.w, s3.n_stages, d.n_lin, d.skip_layer, points, skip_flag, M, sdf_out, grid, st);
     return i2sdf_hip_check(hipGetLastError(), "sdf_forward (bf16x3) launch");
   }
-  if (full && p->sdf_fwd_bf16x3 && H == 256 && F == 256 && span_chunks(p->sdf, SPAN_FWD3H) > 0) {
+  if (full && kind == SDF_FWD_X3H_256) {
     // [sdf | feature] rows (ImplicitNetwork.forward: the meshing callers, model/eval/recon.py:51,90, utils/plots.py:52): the 16-point-wave
     // forward of the training path without its saves -- the same kernel, so the 257 columns are the values a training step computes
     const Span s3 = span(p, packed, p->sdf, SPAN_FWD3H);
@@ -121,14 +114,14 @@ extern "C" int i2sdf_sdf_forward(const i2sdf_plan* p, const float* packed, const
   return I2SDF_EINVAL;
 }
 
-// internal (sampler): sdf at x = cam[r] + z[r*ldz + j]*dirs[r] for j < n_per_ray; whole launch is a no-op when *skip_flag != 0
+// internal (mlp_args.h): the sampler's passes and the stepwise tracer's
 int i2sdf_sdf_forward_rays_flagged(const i2sdf_plan* p, const float* packed, const float* cam, const float* dirs, const float* z, int64_t ldz,
-                                   int32_t n_per_ray, int64_t B, float* sdf_out, const int* skip_flag, void* stream) {
+                                   int32_t n_per_ray, int64_t B, float* sdf_out, const int* skip_flag, bool sampler_pass, void* stream) {
   if (p->sdf.d.multires != 6) return I2SDF_EINVAL;
   const int64_t M = B * n_per_ray;
   const PointSpec ps{nullptr, cam, dirs, z, ldz, M, n_per_ray};
   hipStream_t st = (hipStream_t)stream;
-  if (p->H == 256 && p->F == 256) return launch_sdf_fwd<256, 256, 6>(p, packed, ps, skip_flag, M, sdf_out, nullptr, 0, st, true);
-  if (p->H == 64 && p->F == 64) return launch_sdf_fwd<64, 64, 6>(p, packed, ps, skip_flag, M, sdf_out, nullptr, 0, st, true);
+  if (p->H == 256 && p->F == 256) return launch_sdf_fwd<256, 256, 6>(p, packed, ps, skip_flag, M, sdf_out, nullptr, 0, st, sampler_pass);
+  if (p->H == 64 && p->F == 64) return launch_sdf_fwd<64, 64, 6>(p, packed, ps, skip_flag, M, sdf_out, nullptr, 0, st, sampler_pass);
   return I2SDF_EINVAL;
 }

@@ -16,14 +16,6 @@
 
 using namespace i2sdf;
 
-int i2sdf_hip_check(hipError_t e, const char* what);
-// mlp_fwd.hip: sdf at x = cam[r] + z[r*ldz + j]*dirs[r]; fp32 MFMA kernel, or the 32-point-wave bf16x3 kernel of a 64-wide plan
-int i2sdf_sdf_forward_rays_flagged(const i2sdf_plan* p, const float* packed, const float* cam, const float* dirs, const float* z, int64_t ldz,
-                                   int32_t n_per_ray, int64_t B, float* sdf_out, const int* skip_flag, void* stream);
-// mlp_x3h.hip: the 16-point-wave bf16x3 kernel of a 256-wide plan
-void i2sdf_launch_sdf_fwd3h(const float* stream, int n_stages, int L, int skip, const PointSpec& ps, const int* skip_flag, int64_t M, float* sdf_out,
-                            int planes, hipStream_t st);
-
 namespace {
 
 constexpr int TRACE_THREADS = 256;
@@ -60,21 +52,6 @@ __global__ __launch_bounds__(TRACE_THREADS) void trace_step_kernel(TraceState s,
   if (last && ray.status == I2SDF_TRACE_ACTIVE) ray.status = I2SDF_TRACE_UNRESOLVED;
   s.t[r] = ray.t; s.lo[r] = ray.lo; s.hi[r] = ray.hi;
   s.status[r] = ray.status; s.steps[r] = ray.steps; s.bracketed[r] = ray.bracketed;
-}
-
-// the sdf-only forward of i2sdf_sdf_forward on the points cam + t * dirs.  A 256-wide bf16x3 plan goes to its kernel directly with THREE
-// planes: i2sdf_sdf_forward_rays_flagged is the sampler's entry and would take two under I2SDF_OPT_SAMPLER_BF16X2; on every other plan that
-// option changes nothing and the sampler's entry is the public forward.
-int trace_sdf(const i2sdf_plan* p, const float* packed, const float* cam, const float* dirs, const float* t, int64_t N, float* f, hipStream_t st) {
-  if (p->sdf_fwd_bf16x3 && p->H == 256 && p->F == 256 && p->sdf.d.multires == 6 && span_chunks(p->sdf, SPAN_FWD3H) > 0) {
-    const Span s3 = span(p, packed, p->sdf, SPAN_FWD3H_SDF);
-    if (!s3.n_stages) return I2SDF_EINVAL;
-    const PointSpec ps{nullptr, cam, dirs, t, 1, N, 1};
-    i2sdf_launch_sdf_fwd3h(s3.w, s3.n_stages, p->sdf.d.n_lin, p->sdf.d.skip_layer, ps, nullptr, N, f, 3, st);
-    return i2sdf_hip_check(hipGetLastError(), "trace_rays: sdf forward (bf16x3, 16-point waves) launch");
-  }
-  const int rc = i2sdf_sdf_forward_rays_flagged(p, packed, cam, dirs, t, 1, 1, N, f, nullptr, (void*)st);
-  return rc == I2SDF_EINVAL ? i2sdf_refuse("i2sdf_trace_rays: the plan's SDF net has no sdf-only forward kernel") : rc;
 }
 
 struct TraceArgs {
@@ -227,12 +204,10 @@ __global__ __launch_bounds__(NW * 64, 2) void sdf_trace3h_kernel(const float* __
   }
 }
 
-// which fused kernel the plan has: 0 none, 64 / 256 the width it is built for
+// which fused kernel the plan has: 0 none, 64 / 256 the width it is built for -- they follow the bf16x3 sdf-only forwards
 int fused_kind(const i2sdf_plan* p) {
-  if (!p->sdf_fwd_bf16x3 || p->sdf.d.multires != 6) return 0;
-  if (p->H == 256 && p->F == 256 && span_chunks(p->sdf, SPAN_FWD3H) > 0) return 256;
-  if (p->H == 64 && p->F == 64 && span_chunks(p->sdf, SPAN_FWD3) > 0) return 64;
-  return 0;
+  const SdfFwdKind kind = sdf_fwd_kind(p);
+  return kind == SDF_FWD_X3H_256 ? 256 : kind == SDF_FWD_X3_64 ? 64 : 0;
 }
 
 int trace_fused(const i2sdf_plan* p, const float* packed, const TraceArgs& a, hipStream_t st) {
@@ -285,7 +260,9 @@ extern "C" int i2sdf_trace_rays(const i2sdf_plan* p, const float* packed, const 
   trace_init_kernel<<<grid, TRACE_THREADS, 0, st>>>(s, t_min, t_max, N);
   if (int rc = i2sdf_hip_check(hipGetLastError(), "trace_rays: init launch")) return rc;
   for (int32_t step = 0; step < cfg->max_steps; ++step) {
-    if (int rc = trace_sdf(p, packed, cam, dirs, t_out, N, s.f, st)) return rc;
+    // the sdf-only forward of i2sdf_sdf_forward on the points cam + t * dirs: three planes, never the sampler's two
+    if (int rc = i2sdf_sdf_forward_rays_flagged(p, packed, cam, dirs, t_out, 1, 1, N, s.f, nullptr, false, (void*)st))
+      return rc == I2SDF_EINVAL ? i2sdf_refuse("i2sdf_trace_rays: the plan's SDF net has no sdf-only forward kernel") : rc;
     trace_step_kernel<<<grid, TRACE_THREADS, 0, st>>>(s, t_min, t_max, N, cfg->eps, cfg->step_scale, step, step == cfg->max_steps - 1, f_trace);
     if (int rc = i2sdf_hip_check(hipGetLastError(), "trace_rays: step launch")) return rc;
   }

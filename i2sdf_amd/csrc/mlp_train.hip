@@ -9,9 +9,6 @@
 
 using namespace i2sdf;
 
-int i2sdf_hip_check(hipError_t e, const char* what);
-
-
 namespace {
 
 template <int H, int F, int LF, bool GRAD>
@@ -411,14 +408,9 @@ extern "C" int i2sdf_sdf_forward_grad(const i2sdf_plan* p, const float* packed, 
   // full workgroups in bf16x3 split arithmetic: the forward with saves on 16-point waves (x3h.h, mlp_x3h.hip), the d sdf/dx chain on
   // 32-point waves (x3.h, mlp_x3.hip) -- both read / write the same saved tensors; the split-K tail keeps the fp32 MFMA kernel
   const bool x3 = p->train_fwd_bf16x3 != 0 && wide && d.n_lin >= 4 && d.skip_layer != d.n_lin - 2;
-  SdfTrainFwdArgs a3 = a;
-  if (x3) {
-    const Span fwd3 = span(p, packed, p->sdf, feat ? SPAN_FWD3H : SPAN_FWD3H_SDF), rev3 = span(p, packed, p->sdf, SPAN_REV3_CHAIN);
-    if (!fwd3.n_stages || !rev3.n_stages) return I2SDF_EINVAL;
-    a3.fwd = fwd3.w; a3.n_fwd = fwd3.n_stages; a3.rev = rev3.w; a3.n_rev = rev3.n_stages;
-    a3.kcs = sdf_blocked_points(p, M, Mp, feat != nullptr) > 0 ? KCS_BLK : KCS_PM;
-    a3.p24 = (sdf_saves24(p) && a3.kcs == KCS_BLK && abars != nullptr) ? 1 : 0;
-  }
+  const Span fwd3 = x3 ? span(p, packed, p->sdf, feat ? SPAN_FWD3H : SPAN_FWD3H_SDF) : Span{}, rev3 = x3 ? span(p, packed, p->sdf, SPAN_REV3_CHAIN) : Span{};
+  if (x3 && (!fwd3.n_stages || !rev3.n_stages)) return I2SDF_EINVAL;
+  const int kcs3 = sdf_blocked_points(p, M, Mp, feat != nullptr) > 0 ? KCS_BLK : KCS_PM;
   hipStream_t st = (hipStream_t)stream;
   const bool ranged = x3 && i2sdf_parts_on(p);      // point ranges (plan.h: PartRun): one launch pair per range; no split-K tail
   ChainGuard guard(p, st, ranged);
@@ -428,9 +420,12 @@ extern "C" int i2sdf_sdf_forward_grad(const i2sdf_plan* p, const float* packed, 
     else launch_lds_bytes(KS_LDS_BYTES, sdf_train_fwd_split_kernel<256, 256, 6, false>, g, s, a, m0);
   };
   auto full = [&](hipStream_t s, int wg0, unsigned g, int64_t Mv) {
-    SdfTrainFwdArgs x = x3 ? a3 : a;
+    SdfTrainFwdArgs x = a;
     x.wg0 = wg0; x.M = Mv;
     if (x3) {
+      // what the bf16x3 launches take: their spans, the layout of the saved tensors (the fp32 and split-K launches: the fp32 spans, KCS_PM)
+      x.fwd = fwd3.w; x.n_fwd = fwd3.n_stages; x.rev = rev3.w; x.n_rev = rev3.n_stages;
+      x.kcs = kcs3; x.p24 = (sdf_saves24(p) && kcs3 == KCS_BLK && abars != nullptr) ? 1 : 0;
       i2sdf_launch_train_fwd3h(x, g, s);
       if (grad) i2sdf_launch_igrad3(x, g, s);
     } else if (wide) {
@@ -445,6 +440,62 @@ extern "C" int i2sdf_sdf_forward_grad(const i2sdf_plan* p, const float* packed, 
   return i2sdf_hip_check(hipGetLastError(), "sdf_forward_grad launch");
 }
 
+namespace {
+
+// THE kernel choice of the radiance forward.  tail_m0 < 0: `g` full workgroups from x.wg0 on; tail_m0 >= 0: the split-K form of the fp32
+// 256-wide 'nerf' kernel (ksplit.h) over the points from tail_m0 on, `g` workgroups of 32 points.
+void launch_rgb_fwd(const i2sdf_plan* p, const RgbPath& k, const RgbFwdArgs& x, unsigned g, hipStream_t s, int64_t tail_m0 = -1) {
+  if (!k.idr && k.wide && (!k.x3 || tail_m0 >= 0)) {
+    if (tail_m0 < 0) {
+      if (k.emb) launch_lds(rgb_fwd_kernel<256, 256, 4, false, RgbEmbedFwdArgs>, g, s, with_view_embed(p, x));
+      else launch_lds(rgb_fwd_kernel<256, 256, 4>, g, s, x);
+    } else if (k.emb) launch_lds_bytes(KS_LDS_BYTES, rgb_fwd_split_kernel<256, 256, 4, RgbEmbedFwdArgs>, g, s, with_view_embed(p, x), tail_m0);
+    else launch_lds_bytes(KS_LDS_BYTES, rgb_fwd_split_kernel<256, 256, 4>, g, s, x, tail_m0);
+  } else if (k.x3) {                       // 16-point waves (mlp_x3h.hip)
+    if (k.emb) i2sdf_launch_rgb_fwd3h_embed(with_view_embed(p, x), k.idr, g, s);
+    else if (k.idr) i2sdf_launch_rgb_fwd3h_idr(x, k.enc ? 4 : 0, g, s);
+    else i2sdf_launch_rgb_fwd3h(x, g, s);
+  } else if (!k.idr) {                     // 'nerf', 64 wide
+    if (k.emb) launch_lds(rgb_fwd_kernel<64, 64, 4, false, RgbEmbedFwdArgs>, g, s, with_view_embed(p, x));
+    else launch_lds(rgb_fwd_kernel<64, 64, 4>, g, s, x);
+  } else if (k.emb) {                      // 'idr', fp32
+    if (k.wide) launch_lds(rgb_fwd_kernel<256, 256, 4, true, RgbEmbedFwdArgs>, g, s, with_view_embed(p, x));
+    else launch_lds(rgb_fwd_kernel<64, 64, 4, true, RgbEmbedFwdArgs>, g, s, with_view_embed(p, x));
+  } else if (k.wide) {                     // view directions through PE4, or as they are (embed_type: null)
+    if (k.enc) launch_lds(rgb_fwd_kernel<256, 256, 4, true>, g, s, x);
+    else launch_lds(rgb_fwd_kernel<256, 256, 0, true>, g, s, x);
+  } else if (k.enc) launch_lds(rgb_fwd_kernel<64, 64, 4, true>, g, s, x);
+  else launch_lds(rgb_fwd_kernel<64, 64, 0, true>, g, s, x);
+}
+
+// The radiance forward of either mode behind the entry point's own checks; `a` holds the caller's arguments.  'nerf', 256 wide: the partial
+// last round as split-K workgroups of the fp32 kernel.  'idr': every point goes through full workgroups (rgb_blocked_points covers the whole
+// batch whenever the bf16x3 kernels run, as it does under point ranges).
+int rgb_forward(const i2sdf_plan* p, const float* packed, RgbFwdArgs a, hipStream_t st, const char* what) {
+  const i2sdf_mlp_desc& d = p->rgb.d;
+  RgbPath k;
+  if (!rgb_path(p, &k)) return I2SDF_EINVAL;
+  const bool may_split = k.wide && !k.idr;
+  Span fwd, fwd3;
+  if (!k.x3 || may_split) { fwd = span(p, packed, p->rgb, SPAN_FWD); if (!fwd.n_stages) return I2SDF_EINVAL; }
+  if (k.x3) { fwd3 = span(p, packed, p->rgb, SPAN_FWD3H); if (!fwd3.n_stages) return I2SDF_EINVAL; }
+  a.fwd = fwd.w; a.n_fwd = fwd.n_stages; a.L = d.n_lin; a.act = rgb_act(d);
+  const int kcs3 = rgb_blocked_points(p, a.M, a.Mp) > 0 ? KCS_BLK : KCS_PM;
+  const bool ranged = k.x3 && i2sdf_parts_on(p);
+  ChainGuard guard(p, st, ranged);
+  auto full = [&](hipStream_t s, int wg0, unsigned g, int64_t Mv) {
+    RgbFwdArgs x = a;
+    x.wg0 = wg0; x.M = Mv;
+    if (k.x3) { x.fwd = fwd3.w; x.n_fwd = fwd3.n_stages; x.kcs = kcs3; }      // what the bf16x3 launches take (the others: the fp32 span, KCS_PM)
+    launch_rgb_fwd(p, k, x, g, s);
+  };
+  auto tail = [&](hipStream_t s, int64_t m0) { launch_rgb_fwd(p, k, a, (unsigned)((a.M - m0 + 31) / 32), s, m0); };
+  i2sdf_dispatch_points(p, st, a.M, ranged, may_split, TAIL_BEHIND, full, tail);
+  return i2sdf_hip_check(hipGetLastError(), what);
+}
+
+}  // namespace
+
 extern "C" int i2sdf_rgb_forward(const i2sdf_plan* p, const float* packed, const float* dirs, int32_t n_per_ray, const float* feat,
                                  int64_t M, int64_t Mp, float* rgb, float* rs, float* pev_save, void* stream) {
   if (M == 0) return I2SDF_OK;                 // empty batch: nothing to validate, nothing to launch
@@ -455,48 +506,12 @@ extern "C" int i2sdf_rgb_forward(const i2sdf_plan* p, const float* packed, const
   if ((emb == I2SDF_RGB_EMBED_POSITIONAL && d.multires != 4) || rgb_idr(d)) return I2SDF_EINVAL;          // ('idr' plans: i2sdf_rgb_forward_idr)
   if (emb == I2SDF_RGB_EMBED_FOURIER && !p->view_B_set)
     return i2sdf_refuse("i2sdf_rgb_forward: the plan's Fourier view embedder has no matrix B yet (i2sdf_plan_set_view_embed)");
-  const bool wide = d.hidden == 256 && p->F == 256, x3 = wide && p->rgb_bf16x3;
-  if (!wide && !(d.hidden == 64 && p->F == 64)) return I2SDF_EINVAL;
-  const Span fwd = span(p, packed, p->rgb, SPAN_FWD);
-  if (!fwd.n_stages) return I2SDF_EINVAL;
   RgbFwdArgs a{};
-  a.fwd = fwd.w; a.n_fwd = fwd.n_stages;
-  a.L = d.n_lin; a.dirs = dirs; a.n_per_ray = n_per_ray; a.feat = feat; a.M = M; a.Mp = Mp; a.rgb = rgb; a.rs = rs; a.pev_save = pev_save;
-  a.act = rgb_act(d);
-  // full workgroups optionally in bf16x3 split arithmetic (mlp_x3h.hip); the split-K tail keeps the fp32 MFMA kernel
-  RgbFwdArgs a3 = a;
-  if (x3) {
-    const Span fwd3 = span(p, packed, p->rgb, SPAN_FWD3H);
-    if (!fwd3.n_stages) return I2SDF_EINVAL;
-    a3.fwd = fwd3.w; a3.n_fwd = fwd3.n_stages;
-    a3.kcs = rgb_blocked_points(p, M, Mp) > 0 ? KCS_BLK : KCS_PM;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const bool ranged = x3 && i2sdf_parts_on(p);
-  ChainGuard guard(p, st, ranged);
-  auto full = [&](hipStream_t s, int wg0, unsigned g, int64_t Mv) {
-    RgbFwdArgs x = x3 ? a3 : a;
-    x.wg0 = wg0; x.M = Mv;
-    if (emb) {
-      const RgbEmbedFwdArgs xe = with_view_embed(p, x);
-      if (x3) i2sdf_launch_rgb_fwd3h_embed(xe, false, g, s);
-      else launch_lds(rgb_fwd_kernel<256, 256, 4, false, RgbEmbedFwdArgs>, g, s, xe);
-    } else if (x3) i2sdf_launch_rgb_fwd3h(x, g, s);
-    else launch_lds(rgb_fwd_kernel<256, 256, 4>, g, s, x);
-  };
-  auto tail = [&](hipStream_t s, int64_t m0) {
-    const unsigned g = (unsigned)((M - m0 + 31) / 32);
-    if (emb) launch_lds_bytes(KS_LDS_BYTES, rgb_fwd_split_kernel<256, 256, 4, RgbEmbedFwdArgs>, g, s, with_view_embed(p, a), m0);
-    else launch_lds_bytes(KS_LDS_BYTES, rgb_fwd_split_kernel<256, 256, 4>, g, s, a, m0);
-  };
-  if (wide) i2sdf_dispatch_points(p, st, M, ranged, true, TAIL_BEHIND, full, tail);
-  else if (emb) launch_lds(rgb_fwd_kernel<64, 64, 4, false, RgbEmbedFwdArgs>, (unsigned)((M + PTS_PER_WG - 1) / PTS_PER_WG), st, with_view_embed(p, a));
-  else launch_lds(rgb_fwd_kernel<64, 64, 4>, (unsigned)((M + PTS_PER_WG - 1) / PTS_PER_WG), st, a);
-  return i2sdf_hip_check(hipGetLastError(), "rgb_forward launch");
+  a.dirs = dirs; a.n_per_ray = n_per_ray; a.feat = feat; a.M = M; a.Mp = Mp; a.rgb = rgb; a.rs = rs; a.pev_save = pev_save;
+  return rgb_forward(p, packed, a, (hipStream_t)stream, "rgb_forward launch");
 }
 
-// 'idr' mode (include/i2sdf.h): the same launches over the kernels' IDR instantiations.  No split-K tail: every point goes through full
-// workgroups (rgb_blocked_points covers the whole batch whenever the bf16x3 kernels run, as it does under point ranges).
+// 'idr' mode (include/i2sdf.h): the same launches over the kernels' IDR instantiations
 extern "C" int i2sdf_rgb_forward_idr(const i2sdf_plan* p, const float* packed, const float* points, const float* cam, const float* dirs,
                                      const float* z, int64_t ldz, int32_t n_per_ray, const float* normals, const float* feat, int64_t M,
                                      int64_t Mp, float* rgb, float* rs, float* pev_save, void* stream) {
@@ -509,37 +524,11 @@ extern "C" int i2sdf_rgb_forward_idr(const i2sdf_plan* p, const float* packed, c
   if ((emb == I2SDF_RGB_EMBED_POSITIONAL && d.multires != 4 && d.multires != 0) || !rgb_idr(d)) return I2SDF_EINVAL;
   if (emb == I2SDF_RGB_EMBED_FOURIER && !p->view_B_set)
     return i2sdf_refuse("i2sdf_rgb_forward_idr: the plan's Fourier view embedder has no matrix B yet (i2sdf_plan_set_view_embed)");
-  const bool enc = d.multires == 4;               // view directions through PE4, or as they are (embed_type: null)
-  const bool wide = d.hidden == 256 && p->F == 256, x3 = wide && p->rgb_bf16x3;
-  if (!wide && !(d.hidden == 64 && p->F == 64)) return I2SDF_EINVAL;
-  const Span fwd = span(p, packed, p->rgb, x3 ? SPAN_FWD3H : SPAN_FWD);
-  if (!fwd.n_stages) return I2SDF_EINVAL;
   RgbFwdArgs a{};
-  a.fwd = fwd.w; a.n_fwd = fwd.n_stages;
-  a.L = d.n_lin; a.dirs = dirs; a.n_per_ray = n_per_ray; a.feat = feat; a.M = M; a.Mp = Mp; a.rgb = rgb; a.rs = rs; a.pev_save = pev_save;
-  a.act = rgb_act(d);
+  a.dirs = dirs; a.n_per_ray = n_per_ray; a.feat = feat; a.M = M; a.Mp = Mp; a.rgb = rgb; a.rs = rs; a.pev_save = pev_save;
   a.pts = PointSpec{points, cam, dirs, z, ldz, points ? 0 : M, n_per_ray};
   a.normals = normals;
-  if (x3) a.kcs = rgb_blocked_points(p, M, Mp) > 0 ? KCS_BLK : KCS_PM;
-  hipStream_t st = (hipStream_t)stream;
-  const bool ranged = x3 && i2sdf_parts_on(p);
-  ChainGuard guard(p, st, ranged);
-  auto full = [&](hipStream_t s, int wg0, unsigned g, int64_t Mv) {
-    RgbFwdArgs x = a;
-    x.wg0 = wg0; x.M = Mv;
-    if (emb) {
-      const RgbEmbedFwdArgs xe = with_view_embed(p, x);
-      if (x3) i2sdf_launch_rgb_fwd3h_embed(xe, true, g, s);
-      else if (wide) launch_lds(rgb_fwd_kernel<256, 256, 4, true, RgbEmbedFwdArgs>, g, s, xe);
-      else launch_lds(rgb_fwd_kernel<64, 64, 4, true, RgbEmbedFwdArgs>, g, s, xe);
-    } else if (x3) i2sdf_launch_rgb_fwd3h_idr(x, enc ? 4 : 0, g, s);
-    else if (wide && enc) launch_lds(rgb_fwd_kernel<256, 256, 4, true>, g, s, x);
-    else if (wide) launch_lds(rgb_fwd_kernel<256, 256, 0, true>, g, s, x);
-    else if (enc) launch_lds(rgb_fwd_kernel<64, 64, 4, true>, g, s, x);
-    else launch_lds(rgb_fwd_kernel<64, 64, 0, true>, g, s, x);
-  };
-  i2sdf_dispatch_points(p, st, M, ranged, false, TAIL_BEHIND, full, [](hipStream_t, int64_t) {});
-  return i2sdf_hip_check(hipGetLastError(), "rgb_forward_idr launch");
+  return rgb_forward(p, packed, a, (hipStream_t)stream, "rgb_forward_idr launch");
 }
 
 // =============================================================================================================

@@ -142,6 +142,8 @@ struct i2sdf_plan {
 
 // An entry point's refusal with a reason: the text goes where i2sdf_last_hip_error() finds it; returns I2SDF_EINVAL (plan.cpp)
 int i2sdf_refuse(const char* why);
+// hipSuccess -> I2SDF_OK; anything else -> I2SDF_EHIP, with `what` and the error's text where i2sdf_last_hip_error() finds them (plan.cpp)
+int i2sdf_hip_check(hipError_t e, const char* what);
 
 // ---- spans of the weight streams ----------------------------------------------------------------------------------
 // What a kernel takes: where its weight stream starts and how many LDS stages it walks.  n_stages == 0: the span was refused -- empty

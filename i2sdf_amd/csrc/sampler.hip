@@ -15,11 +15,9 @@
 //                               workgroup to finish raises the "done" flag (no separate launch)
 //     (a caller-fixed iteration count needs no batch flag: sampler_iter_fixed_kernel does both steps in one launch)
 //   sampler_final_kernel      : near/far/extra samples, sort, eikonal sample
-#include "plan.h"
+#include "mlp_args.h"
 
 using namespace i2sdf;
-
-int i2sdf_hip_check(hipError_t e, const char* what);
 
 namespace {
 
@@ -568,8 +566,6 @@ extern "C" int i2sdf_error_bound(const float* z, const float* sdf, int64_t B, in
   return i2sdf_hip_check(hipGetLastError(), "error_bound launch");
 }
 
-int i2sdf_sdf_forward_rays_flagged(const i2sdf_plan* p, const float* packed, const float* cam, const float* dirs, const float* z, int64_t ldz,
-                                   int32_t n_per_ray, int64_t B, float* sdf_out, const int* skip_flag, void* stream);
 
 extern "C" int i2sdf_sample_rays(const i2sdf_plan* p, const float* packed, const float* params, const i2sdf_sampler_cfg* sc,
                                  const float* cam, const float* dirs, int64_t B, int32_t training, const float* t_lin, const float* u_more,
@@ -606,7 +602,7 @@ extern "C" int i2sdf_sample_rays(const i2sdf_plan* p, const float* packed, const
   const int n_it = (force_iters > 0 && force_iters < sc->max_total_iters) ? force_iters : sc->max_total_iters;
   for (int it = 0; it < n_it; ++it) {
     const int n_new = sc->N_samples_eval;
-    int rc = i2sdf_sdf_forward_rays_flagged(p, packed, cam, dirs, samples, NNEW, n_new, B, sdf_new, state + ST_DONE, stream);
+    int rc = i2sdf_sdf_forward_rays_flagged(p, packed, cam, dirs, samples, NNEW, n_new, B, sdf_new, state + ST_DONE, true, stream);
     if (rc) return rc;
     SamplerArgs a{};
     a.B = B; a.it = it; a.n = sc->N_samples_eval * (it + 1); a.n_new = n_new;

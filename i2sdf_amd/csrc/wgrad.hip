@@ -3,13 +3,11 @@
 // In the reference these are the `mm`/`addmm` backward nodes autograd runs for every nn.Linear (mlp.py:97,222) plus
 // the _weight_norm backward.  X, Y are point-major ([Mp][ld]); a wave owns a 128x128 output tile and streams
 // point pairs straight from HBM into MFMA operands (fp32 32x32x2: the reduction index of the MFMA is the point).
-#include <algorithm>
-#include <stdlib.h>
-#include "mlp_common.h"
+// This file holds the kernels and enqueues them; WHICH tasks run in which launch is decided in wgrad_plan.h (host only, printed by
+// tests/wgrad_probe.cpp and pinned by tests/test_wgrad_plan.py).
+#include "wgrad_plan.h"      // the tasks, WgLaunch, the launch plan: host-side, shared with tests/wgrad_probe.cpp
 
 using namespace i2sdf;
-
-int i2sdf_hip_check(hipError_t e, const char* what);
 
 namespace {
 
@@ -30,22 +28,7 @@ namespace {
 #ifndef W3_P24_NT
 #define W3_P24_NT 0      // the packed 24-bit operands' loads: plain (see w3p_job; A/B in profiles/r6_saves24.txt)
 #endif
-constexpr int WG_CH = I2SDF_WG_CH;   // points per split-M chunk (plan.h; plan.cpp: PART_ALIGN -- point ranges are cut at chunk boundaries)
 constexpr int PFW = 6;               // point pairs in flight
-constexpr int MAX_TASKS = 30;
-
-// A / B point at column a_c0 / b_c0 of the operand's first row in the POINT-MAJOR sense; a_blk / b_blk = leading points of the
-// operand tensor stored in the blocked layout (mlp_common.h; only 256-wide tensors, accessed as 128-column tiles, are ever blocked)
-// a_p24 / b_p24: the operand's blocked points are packed 24-bit records (x3.h P24: abars, gus, gas under I2SDF_OPT_SAVES24; only 256-wide tensors,
-// read by the split-arithmetic kernels)
-struct WgJob { const float* A; const float* B; int32_t lda, ldb, a_w, b_w; int64_t m_count; int64_t a_blk, b_blk; int32_t a_c0, b_c0; int32_t a_p24, b_p24; };
-struct WgTask {
-  WgJob j[2];
-  int32_t njobs, relu_b, has_bias, rows_store, cols_store, ldo;
-  int32_t variant, pad;
-  int64_t out_off, bias_off;
-};
-struct WgLaunch { WgTask t[MAX_TASKS]; int32_t n; int32_t chunk0; int64_t chunk_stride; float* partials; };     // chunk0: first chunk of this launch (point ranges)
 
 // AM = 0: A tile 128 wide (16 B per lane, rows 4i+ta)      AM = 1: A narrower than 32 columns (4 B per lane, row i)
 // BM = 0: B tile 128 wide (16 B per lane, cols 4j+tb)      BM = 1 / 2: B at most 32 / 64 columns wide (4 B per lane, col j + 32 tb)
@@ -427,8 +410,6 @@ __global__ __launch_bounds__(64) void wgrad_kernel(WgLaunch L) {
 // workgroups took 0.62 ms per step.
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int PFN = 8;               // 128 point pairs per wave = 8 groups of 16
-constexpr int WGW_SLOT = (16 * 16 + 4) * 64;               // floats of one wave's partial 128x128 tile (+ 4 bias sums) in LDS
-constexpr int WGN_LDS_BYTES = 2 * WGW_SLOT * 4;            // two such slots (wgrad_wide_body) > three narrow partials (3 * (8 * 16 + 4) * 64 * 4)
 
 // NPL = 0: fp32-input MFMA (wgrad_accumulate); 2 / 3: bf16 split arithmetic with that many planes per operand (wgrad_accumulate_x)
 template <int AM, int BM, int NPL, bool A24 = false>
@@ -600,9 +581,9 @@ __global__ __launch_bounds__(256) void wgrad_narrow_kernel(WgLaunch L) {
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const WgTask& t = L.t[blockIdx.y];
   const int64_t chunk = blockIdx.x + L.chunk0;
-  if (NPL != 0 && t.variant == 0) wgrad_wide_body<NPL == 0 ? 3 : NPL>(L, t, chunk, wave, lane, wgn_lds);      // (only the split form gets such tasks)
-  else if (t.variant == 1) wgrad_narrow_body<1, 0, NPL>(L, t, chunk, wave, lane, wgn_lds);
-  else if (t.variant == 2) { if (NPL != 0 && t.j[0].a_p24) wgrad_narrow_body<0, 1, NPL, NPL != 0>(L, t, chunk, wave, lane, wgn_lds); else wgrad_narrow_body<0, 1, NPL>(L, t, chunk, wave, lane, wgn_lds); }
+  if (NPL != 0 && t.variant == WG_TILE) wgrad_wide_body<NPL == 0 ? 3 : NPL>(L, t, chunk, wave, lane, wgn_lds);      // (only the split form gets such tasks)
+  else if (t.variant == WG_NARROW_A) wgrad_narrow_body<1, 0, NPL>(L, t, chunk, wave, lane, wgn_lds);
+  else if (t.variant == WG_NARROW_B32) { if (NPL != 0 && t.j[0].a_p24) wgrad_narrow_body<0, 1, NPL, NPL != 0>(L, t, chunk, wave, lane, wgn_lds); else wgrad_narrow_body<0, 1, NPL>(L, t, chunk, wave, lane, wgn_lds); }
   else { if (NPL != 0 && t.j[0].a_p24) wgrad_narrow_body<0, 2, NPL, NPL != 0>(L, t, chunk, wave, lane, wgn_lds); else wgrad_narrow_body<0, 2, NPL>(L, t, chunk, wave, lane, wgn_lds); }
 }
 
@@ -619,12 +600,8 @@ constexpr int W3_PTS = 16;               // points per stage = one MFMA k-group 
 // run the six leading partial products: 96 MFMAs of 32 cycles per stage and wave, where the fp32 kernel needs 128 of 64 cycles.
 // History: every wave splitting both of its halves in registers (250 VGPRs, twice the VALU work) 1.75 ms; raw rows staged
 // through LDS by LDS-DMA, scheduler-ordered stage 1.55 ms; this version (hand-placed stream, register loads) 1.35 ms, DESIGN.md.
-//   LDS: plane ring 2 x 48 KB = 96 KB.
+//   LDS: plane ring 2 x 48 KB = 96 KB (W3P_SLOTS x W3P_PL floats = W3P_LDS_BYTES, wgrad_plan.h).
 // ---------------------------------------------------------------------------------------------------------------
-constexpr int W3P_PL = 4 * 4 * 3 * 256;                   // floats per plane stage: 4 quarters x 4 tiles x 3 planes x 1 KB (48 KB)
-constexpr int W3P_SLOTS = 2;
-constexpr int W3P_LDS_BYTES = W3P_SLOTS * W3P_PL * 4;      // 96 KB of the CU's 160 KB
-
 // BLKA / BLKB: the A / B operand of this workgroup's chunk is in the blocked layout (compile-time: a runtime select inside the
 // stage costs 5 % through a worse instruction stream).
 // NPL = split planes per operand: 3 = bf16x3 (six partial products, error 2^-24: fp32-equivalent); 2 = bf16x2 (x = x0 + x1, the
@@ -904,15 +881,15 @@ __global__ __launch_bounds__(256) void wgrad3p_kernel(WgLaunch L) {
 }
 
 // ---- ONE launch for every split-arithmetic task of a point range (round 6): the 256x256 blocks (wgrad3p_body) and the narrow / 128x128
-// tasks (wgrad_narrow_body / wgrad_wide_body) as workgroups of the same grid, dispatched on the task's variant.  Two launches per range
+// tasks (wgrad_narrow_body / wgrad_wide_body) as workgroups of the same grid, dispatched on the task's WgVariant.  Two launches per range
 // on one stream ran back to back -- the 250 narrow workgroups alone on their range's stream, not even one round of the chip, then the
 // 475 block workgroups behind a kernel boundary; as one grid of 725 the short narrow workgroups fill the rounds of the long ones.  Both
-// bodies are one workgroup per CU by their registers (460-512) and LDS either way.  Task order: longest first (see the launch site).
+// bodies are one workgroup per CU by their registers (460-512) and LDS either way.  Task order: longest first (wgrad_plan.h: wgrad_passes).
 template <int NPL>
 __global__ __launch_bounds__(256) void wgrad_all_kernel(WgLaunch L) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const WgTask& t = L.t[blockIdx.y];
-  if (t.variant == 4) {
+  if (t.variant == WG_BLOCK) {
     const int64_t m_lo = (int64_t)(blockIdx.x + L.chunk0) * WG_CH;
     bool plain = t.relu_b == 0;
     for (int jb = 0; jb < t.njobs; ++jb) {
@@ -926,20 +903,13 @@ __global__ __launch_bounds__(256) void wgrad_all_kernel(WgLaunch L) {
   // (the narrow blocks always with three planes, as in wgrad_narrow_kernel<3>: bound by their operand reads)
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int64_t chunk = blockIdx.x + L.chunk0;
-  if (t.variant == 0) wgrad_wide_body<3>(L, t, chunk, wave, lane, lds);
-  else if (t.variant == 1) wgrad_narrow_body<1, 0, 3>(L, t, chunk, wave, lane, lds);
-  else if (t.variant == 2) { if (t.j[0].a_p24) wgrad_narrow_body<0, 1, 3, true>(L, t, chunk, wave, lane, lds); else wgrad_narrow_body<0, 1, 3>(L, t, chunk, wave, lane, lds); }
+  if (t.variant == WG_TILE) wgrad_wide_body<3>(L, t, chunk, wave, lane, lds);
+  else if (t.variant == WG_NARROW_A) wgrad_narrow_body<1, 0, 3>(L, t, chunk, wave, lane, lds);
+  else if (t.variant == WG_NARROW_B32) { if (t.j[0].a_p24) wgrad_narrow_body<0, 1, 3, true>(L, t, chunk, wave, lane, lds); else wgrad_narrow_body<0, 1, 3>(L, t, chunk, wave, lane, lds); }
   else { if (t.j[0].a_p24) wgrad_narrow_body<0, 2, 3, true>(L, t, chunk, wave, lane, lds); else wgrad_narrow_body<0, 2, 3>(L, t, chunk, wave, lane, lds); }
 }
 
-// ---- split-M reduction + weight-norm backward: one wave per weight row ------------------------------------
-struct WnLayer {
-  int64_t off_v, off_g, off_bias, blk_off, bias_blk_off;
-  int32_t rows, cols, row0, ldo, rsplit, rbase, split, base1, valid0;
-  float mult;
-};
-struct WnTab { WnLayer l[3 * I2SDF_MAX_LAYERS]; int32_t n; int32_t n_rows; };
-
+// ---- split-M reduction + weight-norm backward: one wave per weight row (WnTab, fill_wn: wgrad_plan.h) ------
 __global__ __launch_bounds__(256) void wn_backward_kernel(WnTab tab, const float* __restrict__ params, const float* __restrict__ partials,
                                                            int n_chunks, int64_t chunk_stride, float* __restrict__ grad) {
   // one block per weight row; wave w sums chunks w, w+4, ... (4x the memory parallelism of one wave per row)
@@ -1011,82 +981,14 @@ __global__ __launch_bounds__(256) void wn_backward_kernel(WnTab tab, const float
   }
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-struct Src { const float* p; int ld; int w; int64_t blk = 0; int p24 = 0; };     // a [Mp][ld] matrix, the width used from it, blocked-prefix points, those as packed 24-bit records
-
-struct TaskList {
-  std::vector<WgTask> tasks;
-  bool quads = false;        // emit one 256x256 task (bf16x3 kernel) where both operands are 256 wide
-  // Emit the tiles of one weight block.  rows: segments of A (one per source, stacked in block rows at row0[i]);
-  // cols: segments of B.  job 0 = (A0[i], B0[k]) over m0 points, job 1 = (A1[i], B1[k]) over m1 points (optional).
-  void add_block(int64_t blk_off, int ldo, int64_t bias_off, const std::vector<Src>& A0, const std::vector<Src>& A1,
-                 const std::vector<int>& row0, const std::vector<int64_t>& mA0, const std::vector<Src>& B0, const std::vector<Src>& B1,
-                 int64_t m1, bool relu_b) {
-    int col0 = 0;
-    for (size_t k = 0; k < B0.size(); ++k) {
-      if (quads && B0[k].w == 256) {
-        for (size_t i = 0; i < A0.size(); ++i) {
-          if (A0[i].w != 256) continue;
-          WgTask t{};
-          t.j[0] = WgJob{A0[i].p, B0[k].p, A0[i].ld, B0[k].ld, 256, 256, mA0[i], A0[i].blk, B0[k].blk, 0, 0, A0[i].p24, B0[k].p24};
-          t.njobs = 1;
-          if (!A1.empty() && A1[i].p != nullptr && !B1.empty()) {
-            t.j[1] = WgJob{A1[i].p, B1[k].p, A1[i].ld, B1[k].ld, 256, 256, m1, A1[i].blk, B1[k].blk, 0, 0, A1[i].p24, B1[k].p24};
-            t.njobs = 2;
-          }
-          t.relu_b = relu_b ? 1 : 0;
-          t.has_bias = (k == 0) ? 1 : 0;
-          t.rows_store = 256; t.cols_store = 256; t.ldo = ldo;
-          t.out_off = blk_off + (int64_t)row0[i] * ldo + col0;
-          t.bias_off = bias_off + row0[i];
-          tasks.push_back(t);
-        }
-      }
-      for (int ct = 0; ct * 128 < B0[k].w; ++ct) {
-        for (size_t i = 0; i < A0.size(); ++i) {
-          if (quads && B0[k].w == 256 && A0[i].w == 256) continue;      // covered by the quad task above
-          for (int rt = 0; rt * 128 < A0[i].w; ++rt) {
-            WgTask t{};
-            const int aw = std::min(128, A0[i].w - rt * 128), bw = std::min(128, B0[k].w - ct * 128);
-            t.j[0] = WgJob{A0[i].p + rt * 128, B0[k].p + ct * 128, A0[i].ld, B0[k].ld, aw, bw, mA0[i], A0[i].blk, B0[k].blk, rt * 128, ct * 128, A0[i].p24, B0[k].p24};
-            t.njobs = 1;
-            if (!A1.empty() && A1[i].p != nullptr && !B1.empty()) {
-              t.j[1] = WgJob{A1[i].p + rt * 128, B1[k].p + ct * 128, A1[i].ld, B1[k].ld, aw, bw, m1, A1[i].blk, B1[k].blk, rt * 128, ct * 128, A1[i].p24, B1[k].p24};
-              t.njobs = 2;
-            }
-            t.relu_b = relu_b ? 1 : 0;
-            t.has_bias = (k == 0 && ct == 0) ? 1 : 0;
-            t.rows_store = aw; t.cols_store = bw; t.ldo = ldo;
-            t.out_off = blk_off + (int64_t)(row0[i] + rt * 128) * ldo + col0 + ct * 128;
-            t.bias_off = bias_off + row0[i] + rt * 128;
-            tasks.push_back(t);
-          }
-        }
-      }
-      col0 += B0[k].w;
-    }
-  }
-};
-
-void fill_wn(WnTab& tab, const NetPlan& np, int kind, int& row0) {
-  const i2sdf_mlp_desc& d = np.d;
-  const bool enc = d.multires > 0 || rgb_idr(d);        // a PE / side block in front of the hidden or feature columns (plan.h: side_dim)
-  const int PED = side_dim(d), PEC8 = enc ? side_chunks(d) * 8 : 0;
-  for (int l = 0; l < d.n_lin; ++l) {
-    WnLayer& y = tab.l[tab.n++];
-    y.off_v = d.off_v[l]; y.off_g = d.off_g[l]; y.off_bias = d.off_bias[l];
-    y.rows = d.out_dim[l]; y.cols = d.in_dim[l]; y.row0 = row0; row0 += y.rows;
-    y.ldo = np.wg_cols[l];
-    y.blk_off = np.wgrad_off[l];
-    y.bias_blk_off = np.wgrad_off[l] + (int64_t)np.wg_rows[l] * np.wg_cols[l];
-    y.rsplit = 1 << 30; y.rbase = 0; y.split = 0; y.base1 = 0; y.valid0 = y.cols; y.mult = 1.0f;
-    const bool last = l == d.n_lin - 1;
-    if (kind == 0) {
-      if (l == d.skip_layer) { y.valid0 = y.cols - PED; y.split = d.hidden; y.base1 = y.cols - PED; y.mult = 0.70710678118654752440f; }
-      if (last) { y.rsplit = 1; y.rbase = 32; }
-    } else if (kind == 1) {
-      if (l == 0) { y.valid0 = PED; y.split = PEC8; y.base1 = PED; }
-    }
+// ---- enqueue one pass (wgrad_plan.h) over the chunks [c_lo, c_hi) on `st`; the LDS attribute is set once per kernel
+void enqueue(WgPass& ps, int c_lo, int c_hi, hipStream_t st) {
+  static void (*const kernels[WGK_COUNT])(WgLaunch) = {wgrad_all_kernel<2>, wgrad_all_kernel<3>, wgrad3p_kernel<2>, wgrad3p_kernel<3>,
+                                                      wgrad_kernel<0, 0>, wgrad_narrow_kernel<3>, wgrad_narrow_kernel<0>};      // by WgKernel
+  static_assert(WGK_COUNT == 7, "one kernel per WgKernel");
+  for (WgLaunch& L : ps.batches) {
+    L.chunk0 = c_lo;
+    launch_dyn_lds(ps.threads, ps.lds_bytes, kernels[ps.kern], dim3((unsigned)(c_hi - c_lo), (unsigned)L.n), st, L);
   }
 }
 
@@ -1102,167 +1004,22 @@ extern "C" int i2sdf_weight_grads(const i2sdf_plan* p, const i2sdf_train_buffers
   const int n_chunks = (int)((Ms + WG_CH - 1) / WG_CH);
   if (n_chunks > n_chunks_cap) return I2SDF_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  TaskList tl;
-  tl.quads = p->wgrad_bf16x3 != 0;
-  {  // ---- SDF net
-    const NetPlan& np = p->sdf;
-    const i2sdf_mlp_desc& d = np.d;
-    const int L = d.n_lin, H = d.hidden, F = p->F, PEC8 = cdiv(d.in0, 8) * 8;
-    const int64_t ls = Mp * H;
-    const int64_t bs = (H == 256) ? sdf_blocked_points(p, Ms, Mp) : 0;      // leading points of hs / abars / gus / gas in the blocked layout
-    const int s24 = (H == 256 && sdf_saves24(p) && bs == Mp) ? 1 : 0;       // abars / gus / gas as packed 24-bit records (hs stays fp32)
-    for (int l = 0; l < L - 1; ++l) {
-      std::vector<Src> B0, B1;
-      if (l == 0) { B0 = {{tb->pe, PEC8, PEC8}}; B1 = {{tb->gpbar, PEC8, PEC8}}; }
-      else {
-        B0 = {{tb->hs + (l - 1) * ls, H, H, bs}}; B1 = {{tb->gus + l * ls, H, H, bs, s24}};
-        if (l == d.skip_layer) { B0.push_back({tb->pe, PEC8, PEC8}); B1.push_back({tb->gpbar, PEC8, PEC8}); }
-      }
-      tl.add_block(np.wgrad_off[l], np.wg_cols[l], np.wgrad_off[l] + (int64_t)np.wg_rows[l] * np.wg_cols[l],
-                   {{tb->gas + l * ls, H, H, bs, s24}}, {{tb->abars + l * ls, H, H, bs, s24}}, {0}, {Ms}, B0, B1, Ms, false);
-    }
-    {
-      const int l = L - 1;
-      std::vector<Src> A0 = {{tb->ga_last4, 4, 4}}, A1 = {{tb->ones4, 4, 4}};
-      std::vector<int> row0 = {0};
-      std::vector<int64_t> mA0 = {Ms};
-      if (F > 0 && Mm > 0 && tb->fbar) { A0.push_back({tb->fbar, F, F}); A1.push_back({nullptr, 0, 0}); row0.push_back(32); mA0.push_back(Mm); }
-      tl.add_block(np.wgrad_off[l], np.wg_cols[l], np.wgrad_off[l] + (int64_t)np.wg_rows[l] * np.wg_cols[l], A0, A1, row0, mA0,
-                   {{tb->hs + (L - 2) * ls, H, H, bs}}, {{tb->gus + (L - 1) * ls, H, H, bs}}, Ms, false);       // (gus[L-1] stays fp32: x3.h X3Sweep2Src)
-    }
-  }
-  if (Mm > 0 && tb->gar) {  // ---- radiance net
-    const NetPlan& np = p->rgb;
-    const i2sdf_mlp_desc& d = np.d;
-    const int L = d.n_lin, H = d.hidden, F = p->F, PV8 = side_chunks(d) * 8;
-    const int64_t ls = Mp * H;
-    const int64_t br = (H == 256) ? rgb_blocked_points(p, Mm, Mp) : 0;     // leading points of rs / gar in the blocked layout
-    for (int l = 0; l < L; ++l) {
-      std::vector<Src> B0;
-      if (l == 0) B0 = {{tb->pev, PV8, PV8}, {tb->feat, F, F}};
-      else B0 = {{tb->rs + (l - 1) * ls, H, H, br}};
-      std::vector<Src> A0;
-      if (l < L - 1) A0 = {{tb->gar + l * ls, H, H, br}};
-      else A0 = {{tb->ga_last_rgb, 4, 4}};
-      tl.add_block(np.wgrad_off[l], np.wg_cols[l], np.wgrad_off[l] + (int64_t)np.wg_rows[l] * np.wg_cols[l], A0, {}, {0}, {Mm}, B0, {}, 0,
-                   false);
-    }
-  }
-  const bool has_light = p->light.d.n_lin > 0 && Mm > 0 && tb->gal0;
-  if (has_light) {  // ---- light head: l=0: A = G(a_0), B = relu(feature) ; l=1: A = G(a_1), B = softplus acts
-    const NetPlan& np = p->light;
-    const int H = np.d.hidden, F = p->F;
-    tl.add_block(np.wgrad_off[0], np.wg_cols[0], np.wgrad_off[0] + (int64_t)np.wg_rows[0] * np.wg_cols[0], {{tb->gal0, H, H}}, {}, {0}, {Mm},
-                 {{tb->feat, F, F}}, {}, 0, true);
-    tl.add_block(np.wgrad_off[1], np.wg_cols[1], np.wgrad_off[1] + (int64_t)np.wg_rows[1] * np.wg_cols[1], {{tb->gal_last, 4, 4}}, {}, {0},
-                 {Mm}, {{tb->hl, H, H}}, {}, 0, false);
-  }
-  // group the tiles by operand shape (narrow operands run 4x / 2x fewer MFMAs per point pair), longest first inside a group
-  auto variant = [](const WgTask& x) {
-    return x.j[0].a_w == 256 ? 4 : (x.j[0].a_w <= 32 ? 1 : (x.j[0].b_w <= 32 ? 2 : (x.j[0].b_w <= 64 ? 3 : 0)));
-  };
-  for (WgTask& x : tl.tasks) x.variant = variant(x);
-  hipStream_t st_main = st;
-  int c_lo = 0, c_hi = n_chunks;             // chunk range of the launches below (point ranges: one range at a time)
-  auto launch = [&](const std::vector<WgTask>& sel, int var) {
-    for (size_t off = 0; off < sel.size(); off += MAX_TASKS) {
-      WgLaunch L{};
-      L.n = (int32_t)std::min<size_t>(MAX_TASKS, sel.size() - off);
-      for (int i = 0; i < L.n; ++i) L.t[i] = sel[off + i];
-      L.chunk_stride = p->wgrad_floats; L.partials = partials;
-      L.chunk0 = c_lo;
-      dim3 grid((unsigned)(c_hi - c_lo), (unsigned)L.n);
-      if (var == 5) {          // split arithmetic: every task of the range in one grid (wgrad_all_kernel)
-        constexpr int LB = W3P_LDS_BYTES > WGN_LDS_BYTES ? W3P_LDS_BYTES : WGN_LDS_BYTES;
-        if (p->wgrad_bf16x2) {
-          (void)hipFuncSetAttribute((const void*)wgrad_all_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, LB);
-          wgrad_all_kernel<2><<<grid, 256, LB, st>>>(L);
-        } else {
-          (void)hipFuncSetAttribute((const void*)wgrad_all_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, LB);
-          wgrad_all_kernel<3><<<grid, 256, LB, st>>>(L);
-        }
-      } else if (var == 4) {
-        if (p->wgrad_bf16x2) {
-          (void)hipFuncSetAttribute((const void*)wgrad3p_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, W3P_LDS_BYTES);
-          wgrad3p_kernel<2><<<grid, 256, W3P_LDS_BYTES, st>>>(L);
-        } else {
-          (void)hipFuncSetAttribute((const void*)wgrad3p_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, W3P_LDS_BYTES);
-          wgrad3p_kernel<3><<<grid, 256, W3P_LDS_BYTES, st>>>(L);
-        }
-      } else if (var == 0) {
-        wgrad_kernel<0, 0><<<grid, 64, 0, st>>>(L);
-      } else {
-        // the narrow blocks (PE columns of layer 0 / the skip layer, the output rows): bf16 split with THREE planes whenever the 256x256
-        // blocks run in split arithmetic, else fp32-input MFMA.  Also under I2SDF_OPT_WGRAD_BF16X2: the kernel is bound by its operand
-        // reads (4.0-4.7 TB/s, matrix pipe 8-16 % busy), so the third plane costs little and these few blocks keep fp32-equivalent
-        // gradients (measured: 107 us per launch with two planes, 127 us with three: +0.03 ms per step).
-        if (p->wgrad_bf16x3) {
-          (void)hipFuncSetAttribute((const void*)wgrad_narrow_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, WGN_LDS_BYTES);
-          wgrad_narrow_kernel<3><<<grid, 256, WGN_LDS_BYTES, st>>>(L);
-        } else {
-          (void)hipFuncSetAttribute((const void*)wgrad_narrow_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, WGN_LDS_BYTES);
-          wgrad_narrow_kernel<0><<<grid, 256, WGN_LDS_BYTES, st>>>(L);
-        }
-      }
-    }
-  };
-  std::vector<WgTask> sel_narrow, sel_blocks[2];
-  // in split arithmetic the 128 x 128 tiles of blocks that are not 256 x 256 (variant 0: the light-mask head) join the 4-wave launch,
-  // in front (the longest tasks): wgrad_wide_body
-  const bool wide_in_narrow = p->wgrad_bf16x3 != 0;
-  if (wide_in_narrow)
-    for (const WgTask& x : tl.tasks) if (x.variant == 0) sel_narrow.push_back(x);
-  for (int var : {3, 1, 2})      // all narrow tiles in one launch, the longest (most MFMAs per point pair, two jobs) first
-    for (int nj = 2; nj >= 1; --nj)
-      for (const WgTask& x : tl.tasks) if (x.variant == var && x.njobs == nj) sel_narrow.push_back(x);
-  for (int v = 0; v < 2; ++v) {
-    for (const WgTask& x : tl.tasks) if (x.variant == (v == 0 ? 4 : 0) && !(v == 1 && wide_in_narrow)) sel_blocks[v].push_back(x);
-    std::stable_sort(sel_blocks[v].begin(), sel_blocks[v].end(), [](const WgTask& x, const WgTask& y) { return x.njobs > y.njobs; });
-  }
-  // split arithmetic: narrow tasks + 256x256 blocks as ONE grid per range (I2SDF_WGRAD_MERGED=0: the two launches of rounds 4-5, for A/B runs)
-  static const bool merged_env = [] { const char* e = getenv("I2SDF_WGRAD_MERGED"); return !(e && e[0] == '0'); }();
-  const bool merged = merged_env && p->wgrad_bf16x3 != 0 && sel_narrow.size() + sel_blocks[0].size() <= (size_t)MAX_TASKS && !sel_blocks[0].empty();
-  std::vector<WgTask> sel_all;
-  // order inside the grid: workgroups are dispatched task by task.  LONGEST FIRST -- the two-job 256x256 tasks, the one-job ones, then the short
-  // narrow tasks, which fill the last round: i2sdf_weight_grads 0.95-0.96 -> 0.91-0.92 ms against narrow-first (three interleaved repetitions in
-  // one GPU call, profiles/r6_launch_chain_ab.txt); I2SDF_WGRAD_BLOCKS_FIRST=0 restores narrow-first for A/B runs
-  static const bool blocks_first = [] { const char* e = getenv("I2SDF_WGRAD_BLOCKS_FIRST"); return !(e && e[0] == '0'); }();
-  if (merged) {
-    if (blocks_first) { sel_all = sel_blocks[0]; sel_all.insert(sel_all.end(), sel_narrow.begin(), sel_narrow.end()); }
-    else { sel_all = sel_narrow; sel_all.insert(sel_all.end(), sel_blocks[0].begin(), sel_blocks[0].end()); }
-  }
   PartRun pr;
-  if (i2sdf_parts_on(p) && i2sdf_parts_begin(p, st_main, Ms, &pr)) {
+  const bool ranged = i2sdf_parts_on(p) && i2sdf_parts_begin(p, st, Ms, &pr);
+  std::vector<WgPass> passes = wgrad_passes(p, tb, partials, ranged);
+  if (ranged) {
     // point ranges (plan.h: PartRun): the GEMMs of a range's chunks on the range's stream, behind that range's backward sweeps
     for (int q = 0; q < pr.n; ++q) {
       if (pr.hi[q] <= pr.lo[q]) continue;
-      c_lo = (int)(pr.lo[q] / WG_CH); c_hi = (int)((pr.hi[q] + WG_CH - 1) / WG_CH);
-      st = pr.st[q];
-      if (merged) launch(sel_all, 5);
-      else {
-        launch(sel_narrow, 1);               // (the narrow blocks behind the 256x256 ones instead: +0.02 ms, measured)
-        launch(sel_blocks[0], 4);
-      }
-      launch(sel_blocks[1], 0);
+      for (WgPass& ps : passes) enqueue(ps, (int)(pr.lo[q] / WG_CH), (int)((pr.hi[q] + WG_CH - 1) / WG_CH), pr.st[q]);
     }
-    st = st_main; c_lo = 0; c_hi = n_chunks;
-    i2sdf_parts_join_all(p, st_main);                   // the reduction below reads every chunk's partials (also ends a chain's ranges)
+    i2sdf_parts_join_all(p, st);                        // the reduction below reads every chunk's partials (also ends a chain's ranges)
   } else {
-    hipStream_t side = i2sdf_tail_fork(p, st_main);
-    st = side;
-    launch(sel_narrow, 1);
-    st = st_main;
-    launch(sel_blocks[0], 4);
-    launch(sel_blocks[1], 0);
-    i2sdf_tail_join(p, st_main, side);
+    hipStream_t side = i2sdf_tail_fork(p, st);
+    for (WgPass& ps : passes) enqueue(ps, 0, n_chunks, ps.side ? side : st);
+    i2sdf_tail_join(p, st, side);
   }
-  WnTab tab{};
-  int row0 = 0;
-  fill_wn(tab, p->sdf, 0, row0);
-  if (Mm > 0 && tb->gar) fill_wn(tab, p->rgb, 1, row0);
-  if (has_light) fill_wn(tab, p->light, 2, row0);
-  tab.n_rows = row0;
-  wn_backward_kernel<<<row0, 256, 0, st>>>(tab, params, partials, n_chunks, p->wgrad_floats, grad_flat);
+  const WnTab tab = wgrad_wn_tab(p, tb);
+  wn_backward_kernel<<<tab.n_rows, 256, 0, st>>>(tab, params, partials, n_chunks, p->wgrad_floats, grad_flat);
   return i2sdf_hip_check(hipGetLastError(), "weight_grads launch");
 }
-
