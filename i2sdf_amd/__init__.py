@@ -34,7 +34,7 @@ def __getattr__(name):
     if name in ("RenderingLayer", "get_rendering_parameters", "shade_draws"):
         from . import shading
         return getattr(shading, name)
-    if name in ("KMeans", "kmeans_pp_centroid"):
+    if name in ("KMeans", "kmeans_pp_centroid", "DBSCAN", "dbscan_seeds"):
         from . import cluster
         return getattr(cluster, name)
     if name in ("SphereTracer", "TraceResult", "TraceResultF"):

@@ -1,8 +1,9 @@
 """Clustering of the emitter point cloud (the reference's `I2SDFNetwork.init_emission_groups`, model/network/__init__.py:49-75):
 `kmeans_pp_centroid` (utils/__init__.py:111-123) and `KMeans` (the part of fast_pytorch_kmeans.KMeans the reference uses) on the device,
-and the host-side DBSCAN seeding the reference offers as an alternative.
+and the DBSCAN seeding the reference offers as an alternative: on the host with scikit-learn as there, or on the device (`DBSCAN`,
+csrc/dbscan.hip: the library's labels for the whole cloud, no scikit-learn).
 
-Both device routes are HIP (csrc/kmeans.hip; include/i2sdf.h states the laws): stream-ordered, without a host read, seeded and bitwise
+The k-means routes are HIP (csrc/kmeans.hip; include/i2sdf.h states the laws): stream-ordered, without a host read, seeded and bitwise
 reproducible.  Imitated: the seeding law (probability proportional to the distance to the nearest centroid so far), Lloyd's iteration with
 the library's stopping rule, empty-cluster rule and returned labels.  Not imitated: numpy's random stream, minibatch k-means, cosine
 mode, dimensions other than 3, and the library's default initialisation (see `KMeans.fit_predict`).
@@ -129,13 +130,106 @@ class KMeans:
         return (labels, d2) if return_dist2 else labels
 
 
-def dbscan_seeds(points, n_emitters: int, n_samples: int = 10000, generator: Optional[torch.Generator] = None) -> torch.Tensor:
-    """The reference's host-side seeding (model/network/__init__.py:50-65): torch.randperm takes n_samples points, sklearn's DBSCAN with
-    its defaults labels them, and each cluster's seed is the first sampled point carrying its label.  -> (n_emitters, 3) float32 on the
-    host.  Runs on the host whatever device `points` is on (it is a set-up call).
+class DBSCAN:
+    """sklearn.cluster.DBSCAN(eps=0.5, min_samples=5) on the device for (n, 3) float32 clouds: euclidean, no sample weights.  The law
+    is stated in include/i2sdf.h ("Density clustering"): the library's labels and core points, with distances formed in fp64.  The whole
+    cloud is clustered in a workspace linear in n (csrc/dbscan.hip); every result is bitwise reproducible."""
+
+    def __init__(self, eps: float = 0.5, min_samples: int = 5):
+        eps = float(eps)
+        if not (eps > 0 and eps * eps > 0 and eps * eps < float("inf")):
+            raise ValueError(f"DBSCAN: needs a finite eps > 0, got {eps}")
+        if int(min_samples) != min_samples or not (1 <= int(min_samples) < 2 ** 31):
+            raise ValueError(f"DBSCAN: needs an integer min_samples in 1 .. 2^31 - 1, got {min_samples}")
+        self.eps, self.min_samples = eps, int(min_samples)
+        self.labels_: Optional[torch.Tensor] = None              # device int64 (n,): cluster numbers, -1 = noise
+        self.core_sample_mask_: Optional[torch.Tensor] = None    # device bool (n,)
+        self.n_clusters_: Optional[torch.Tensor] = None          # device int32 (1,)
+        self.status_: Optional[torch.Tensor] = None              # device int32 (1,): bit 0 non-finite points, bit 1 beyond 2^21 cells
+
+    @property
+    def core_sample_indices_(self) -> torch.Tensor:
+        """indices of the core points, ascending (device int64; sized by the mask, so this waits for the device)"""
+        if self.core_sample_mask_ is None:
+            raise RuntimeError("DBSCAN.core_sample_indices_: nothing fitted yet (call fit_predict)")
+        return torch.nonzero(self.core_sample_mask_).reshape(-1)
+
+    def fit_predict(self, X: torch.Tensor, check: bool = True) -> torch.Tensor:
+        """-> labels (n,) int64 on X's device; labels_, core_sample_mask_, n_clusters_, status_ are set.  Two library calls around one
+        stable torch.sort of the cell keys, all on the current stream.  check=True reads status_ once and raises ValueError for
+        non-finite points or a cloud beyond 2^21 cells of eps / 2 per axis; check=False only enqueues (such points end as -1 and
+        status_ says why)."""
+        X = _points(X, "X")
+        n, dev = int(X.shape[0]), X.device
+        if not (1 <= n < 2 ** 31):
+            raise ValueError(f"DBSCAN.fit_predict: needs 1 <= n < 2^31, got n = {n}")
+        lib = L_.load()
+        ws = torch.empty(int(lib.i2sdf_dbscan_workspace_bytes(n)), dtype=torch.uint8, device=dev)
+        keys = torch.empty(n, dtype=torch.int64, device=dev)
+        labels = torch.empty(n, dtype=torch.int64, device=dev)
+        core = torch.empty(n, dtype=torch.uint8, device=dev)
+        n_clusters = torch.zeros(1, dtype=torch.int32, device=dev)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            L_.check(lib.i2sdf_dbscan_cell_keys(L_.ptr(X), n, self.eps, L_.ptr(ws), L_.ptr(keys), L_.ptr(status), L_.stream_ptr()),
+                     "i2sdf_dbscan_cell_keys")
+            skeys, perm = torch.sort(keys, stable=True)
+            L_.check(lib.i2sdf_dbscan_label(L_.ptr(X), n, self.eps, self.min_samples, L_.ptr(skeys), L_.ptr(perm), L_.ptr(ws), L_.ptr(labels),
+                                            L_.ptr(core), L_.ptr(n_clusters), L_.ptr(status), L_.stream_ptr()), "i2sdf_dbscan_label")
+        self.labels_, self.core_sample_mask_, self.n_clusters_, self.status_ = labels, core.bool(), n_clusters, status
+        if check:
+            _raise_status(int(status), self.eps)
+        return labels
+
+
+def _raise_status(status: int, eps: float):
+    if status & L_.DBSCAN_NONFINITE:
+        raise ValueError("DBSCAN: the points hold non-finite coordinates (such points are labelled -1)")
+    if status & L_.DBSCAN_CELLS:
+        raise ValueError(f"DBSCAN: the cloud spans more than 2^21 cells of eps / 2 = {0.5 * eps:g} along an axis (the 2^21-cell limit): "
+                         "nothing was clustered")
+
+
+def _device_seeds(points, n_emitters, n_samples, generator):
+    pts = _points(points, "points")
+    n, dev = int(pts.shape[0]), pts.device
+    if n_samples is None:
+        samples = pts                                            # the whole cloud in its own order
+    else:
+        pick = torch.randperm(n, generator=generator)[:n_samples]      # the host route's draw
+        samples = pts[pick.to(dev)]
+    db = DBSCAN()
+    labels = db.fit_predict(samples, check=False)
+    found, noise, status = torch.cat([db.n_clusters_.long(), (labels < 0).sum().reshape(1), db.status_.long()]).tolist()      # the one host read
+    _raise_status(status, db.eps)
+    if noise:
+        raise ValueError(f"DBSCAN marked {noise} of {labels.numel()} sampled points as noise: no seed can be taken per cluster "
+                         "(the reference would seed the last cluster with point 0)")
+    if found != int(n_emitters):
+        raise ValueError(f"inconsistent emitter count: n_emitters = {n_emitters}, DBSCAN found {found} clusters")
+    m = labels.numel()
+    first = torch.full((found,), m, dtype=torch.int64, device=dev)
+    first.scatter_reduce_(0, labels, torch.arange(m, dtype=torch.int64, device=dev), "amin")      # first sampled point of every cluster
+    return samples[first].contiguous()
+
+
+def dbscan_seeds(points, n_emitters: int, n_samples: Optional[int] = 10000, generator: Optional[torch.Generator] = None,
+                 route: str = "host") -> torch.Tensor:
+    """The reference's DBSCAN seeding (model/network/__init__.py:50-65): torch.randperm takes n_samples points, DBSCAN with the library's
+    defaults (eps 0.5, min_samples 5) labels them, and each cluster's seed is the first sampled point carrying its label.
+    -> (n_emitters, 3) float32.
+
+    route="host": sklearn's DBSCAN on the host whatever device `points` is on; the seeds are on the host; needs scikit-learn.
+    route="device": the same pick labelled by `DBSCAN` above on the points' ROCm device; the seeds stay there; no scikit-learn, no
+    download of the points.  n_samples=None takes the whole cloud in its own order.  One host read (the cluster count,
+    the noise count and the status word together): it is a set-up call.
 
     Raises ValueError where the reference prints and exits (DBSCAN found another number of clusters than n_emitters), and also when
     DBSCAN reports noise points: the reference counts the noise label as a cluster and then seeds the last cluster with point 0."""
+    if route == "device":
+        return _device_seeds(points, n_emitters, n_samples, generator)
+    if route != "host":
+        raise ValueError(f"dbscan_seeds: route is 'host' or 'device', got {route!r}")
     try:
         from sklearn.cluster import DBSCAN
     except ImportError as e:

@@ -91,6 +91,7 @@ SSIM_TILE_X, SSIM_TILE_Y = 32, 16    # I2SDF_SSIM_TILE_X, I2SDF_SSIM_TILE_Y
 BUBBLE_MAX_K = 4096              # I2SDF_BUBBLE_MAX_K
 BUBBLE_WS_PASSES_OFFSET = 24     # I2SDF_BUBBLE_WS_PASSES_OFFSET
 KMEANS_MAX_K = 256               # I2SDF_KMEANS_MAX_K
+DBSCAN_NONFINITE, DBSCAN_CELLS = 1, 2    # I2SDF_DBSCAN_*: status bits
 TRACE_HIT, TRACE_MISS, TRACE_UNRESOLVED, TRACE_INSIDE = 1, 2, 3, 4      # I2SDF_TRACE_*: status of a traced ray
 TRACE_ROUTES = {"auto": 0, "stepwise": 1, "fused": 2}                   # I2SDF_TRACE_AUTO / _STEPWISE / _FUSED
 TRACE_MAX_STEPS = 1024           # I2SDF_TRACE_MAX_STEPS
@@ -262,6 +263,11 @@ SIGNATURES = {
     "i2sdf_kmeans_fit": (C.c_int, [_P, _I64, _I64, _P, _I32, _D, _P, _P, _P, _P]),
     # points, n, centroids, k, labels, dist2, stream
     "i2sdf_kmeans_assign": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _P]),
+    "i2sdf_dbscan_workspace_bytes": (_I64, [_I64]),
+    # points, n, eps, workspace, keys, status, stream
+    "i2sdf_dbscan_cell_keys": (C.c_int, [_P, _I64, _D, _P, _P, _P, _P]),
+    # points, n, eps, min_samples, sorted_keys, perm, workspace, labels, core, n_clusters, status, stream
+    "i2sdf_dbscan_label": (C.c_int, [_P, _I64, _D, _I32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "i2sdf_trace_workspace_floats": (_I64, [_I64]),
     # plan, packed, cfg, cam, dirs, t_min, t_max, N, t_out, status_out, steps_out, f_trace, workspace, stream
     "i2sdf_trace_rays": (C.c_int, [_P, _P, C.POINTER(TraceCfg)] + [_P] * 4 + [_I64] + [_P] * 6),

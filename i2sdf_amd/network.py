@@ -388,19 +388,25 @@ class I2SDFNetwork(nn.Module):
     def get_param_groups(self, lr):
         return [{"params": self.parameters(), "lr": lr}]
 
-    def init_emission_groups(self, n_emitters: int, pointcloud: torch.Tensor, init_emission: float = 1.0, use_dbscan: bool = False,
+    def init_emission_groups(self, n_emitters: int, pointcloud: torch.Tensor, init_emission: float = 1.0, use_dbscan=False,
                              seed: Optional[int] = None):
         """model/network/__init__.py:49-75: cluster the emitter point cloud (n, 3) -- the light-mask pixels un-projected by depth -- into
         n_emitters groups and create the trainable `emissions` (n_emitters, 3) = init_emission.  -> (labels (n,) int64, centroids
         (n_emitters, 3)); the clustering stays in `self.emitter_clusters` (i2sdf_amd.cluster.KMeans: `.predict`, `.centroids`).
 
         The seeds are k-means++ draws on the device (`seed`: 64 bits, None takes 62 bits from torch's CPU generator), or with use_dbscan
-        the reference's host-side route (i2sdf_amd.cluster.dbscan_seeds; needs scikit-learn).  Lloyd's iteration runs on the device
+        the reference's DBSCAN route (i2sdf_amd.cluster.dbscan_seeds): use_dbscan=True labels the 10 000 sampled points on the host
+        (needs scikit-learn), use_dbscan="device" labels them on the module's device (i2sdf_amd.cluster.DBSCAN; no scikit-learn, no
+        download).  Any other value is refused.  Lloyd's iteration runs on the device
         either way.  `emissions` is created on the module's device (the reference leaves it on the CPU), is in state_dict() under the
         reference's key and in get_param_groups(), and is NOT part of the flat parameter buffer: no render or loss route reads it."""
-        from .cluster import KMeans, dbscan_seeds, kmeans_pp_centroid
+        from .cluster import KMeans, _points, dbscan_seeds, kmeans_pp_centroid
+        if not (isinstance(use_dbscan, bool) or use_dbscan == "device"):
+            raise ValueError(f"init_emission_groups: use_dbscan is False, True (host) or 'device', got {use_dbscan!r}")
         dev = self._param_list()[0].device
-        if use_dbscan:
+        if use_dbscan == "device" and not isinstance(use_dbscan, bool):
+            init_centroids = dbscan_seeds(_points(pointcloud, "pointcloud", dev), n_emitters, route="device")
+        elif use_dbscan:
             init_centroids = dbscan_seeds(pointcloud, n_emitters).to(pointcloud.device)
         else:
             init_centroids = kmeans_pp_centroid(pointcloud, n_emitters, seed)

@@ -1136,6 +1136,66 @@ int i2sdf_kmeans_fit(const float* points, int64_t n, int64_t k, float* centroids
 int i2sdf_kmeans_assign(const float* points, int64_t n, const float* centroids, int64_t k, int64_t* labels, float* dist2, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Density clustering -- the `use_dbscan` seeding of I2SDFNetwork.init_emission_groups (model/network/__init__.py:50-65, where
+ * sklearn.cluster.DBSCAN labels 10 000 sampled points on the host) for the whole cloud on the device.  csrc/dbscan.hip.  No plan.
+ * Every call only enqueues on `stream`: no allocation, no synchronisation, no host read.  No (n, n) or neighbour-list storage: the
+ * workspace is linear in n.
+ *
+ * The law.  points (n, 3) fp32, 1 <= n < 2^31, eps > 0, min_samples >= 1.
+ *   Distance.  d2(i, j) = dx*dx + dy*dy + dz*dz: differences, products and sums in fp64 on the fp64 images of the fp32 coordinates,
+ *              each rounded on its own (no FMA) and added x, y, z left to right.  i and j are neighbours iff d2 <= eps*eps, eps*eps
+ *              formed once in fp64.  The bound is inclusive.
+ *   Core.      core[i] iff at least min_samples points j, i itself counted, are neighbours of i.
+ *   Clusters.  A cluster is a connected component of the core points under the neighbour relation.  Clusters are numbered 0, 1, ... by
+ *              ascending smallest original index of their CORE points; a core point carries its cluster's number.
+ *   Border.    A non-core point with at least one core neighbour carries the smallest number among its core neighbours' clusters.
+ *   Noise.     Every other point is -1.
+ *   Non-finite.  A point with a non-finite coordinate is -1, is nobody's neighbour, and sets status bit 0.
+ * This is a RESTATEMENT of sklearn.cluster.DBSCAN(eps, min_samples).fit(X) (labels_, core_sample_indices_): the library expands
+ * clusters depth first, serially, in index order, so its cluster numbers ascend with the first core point and a contested border point
+ * goes to the cluster expanded first.  It was checked against the library (scikit-learn 1.7.2) where the library was importable:
+ * tests/test_dbscan_ref.py holds the numpy form of the law (tests/dbscan_ref.py) to the library, tests/test_gpu_dbscan.py the device
+ * to that form, exactly.  Not offered: metric, algorithm, leaf_size, p, sample_weight; dimensions other than 3.
+ *
+ * How it is computed (results do not depend on it; all four outputs are order-free functions of the input, so bitwise reproducible).
+ *   Cells.  lo = the per-axis minimum of the finite points; cell edge c = (eps / 2)(1 + 2^-20); cell coordinate floor((p - lo) / c) in
+ *     fp64; 21 bits per axis in one int64 key.  A quotient below 2^21 carries an absolute error below 2^-31 (two roundings of 2^-53).
+ *     (a) Two points of one cell are neighbours: their quotients share a unit interval, so they differ by less than c (1 + 2^-30) on
+ *         every axis, and d2 < 3 c^2 (1 + 2^-29) < 0.7501 eps^2 (the cell's diagonal is 0.867 eps).
+ *     (b) Two neighbours lie at most 2 cells apart on every axis: |dx| <= eps (1 + 2^-52) gives quotients at most
+ *         2 / (1 + 2^-20) + 2^-30 < 2 - 9e-7 apart, so their floors differ by at most 2 -- also for pairs at exactly eps on a lattice,
+ *         whatever the rounding of the quotient: the 2^-20 of slack in c is a thousand times that rounding.
+ *     So a point's neighbours are in the 5 x 5 x 5 cells around its own.  A coordinate beyond 2^21 cells sets status bit 1; such a call
+ *     yields all labels -1, core 0 and n_clusters 0.  The cells are sparse: i2sdf_dbscan_cell_keys writes one key per point, the CALLER
+ *     sorts them (stable, ascending, with the permutation: torch.sort), and i2sdf_dbscan_label finds the run heads, scans them and keeps
+ *     the unique keys; a neighbour cell is a binary search in those, done once per occupied cell (by the wave that owns the cell), not
+ *     once per point.  No dense cell table: two blobs 10^4 apart at eps = 0.01 cost no more than their points.
+ *   Core.  A cell holding min_samples points or more makes all of them core by (a), without a distance; any other point counts its
+ *     neighbours over the 125 cells and stops at min_samples.
+ *   Unions, on original indices, lock-free (csrc/unionfind.h): the core points of a cell are hooked to the smallest of them; for two
+ *     neighbouring cells whose roots differ when looked at, one core pair within eps is searched, the search ends at the first hit and
+ *     unites the two.  A larger root is hooked under a smaller one by compare-and-swap, so the final root is the component's smallest
+ *     core index whatever the schedule.  No kernel waits for another workgroup; a retry follows only a lost compare-and-swap.
+ *   Labels.  A flag at every root, an exclusive scan, n_clusters = its total; a core point takes rank[root]; a non-core point the
+ *     smallest rank over the neighbour cells holding a core point within eps of it.
+ *
+ * i2sdf_dbscan_cell_keys: keys (n) int64 (INT64_MAX for a point without a cell); *status = the status bits.
+ * i2sdf_dbscan_label: sorted_keys, perm (n) int64 = the stable ascending sort of keys and its permutation; the SAME points, n, eps and
+ *   workspace as the call that wrote the keys.  labels (n) int64, core (n) uint8 (0 / 1), *n_clusters, *status int32 (the same bits
+ *   again).  A perm entry outside [0, n) is never dereferenced: its sorted entry holds no point.
+ * workspace: i2sdf_dbscan_workspace_bytes(n) bytes: 0 for n < 1 or n >= 2^31, otherwise a multiple of 16, monotone in n and at most
+ *   96 n + 65536 (about 41 n); 16-byte aligned; the contents before i2sdf_dbscan_cell_keys do not matter.
+ * Refused with I2SDF_EINVAL before any launch: a NULL or misaligned pointer (stream excepted), n outside the range, eps not finite and
+ *   positive (or eps*eps not), min_samples < 1.
+ * ---------------------------------------------------------------------------------------------- */
+#define I2SDF_DBSCAN_NONFINITE 1      /* status bit 0 */
+#define I2SDF_DBSCAN_CELLS 2          /* status bit 1 */
+int64_t i2sdf_dbscan_workspace_bytes(int64_t n);
+int i2sdf_dbscan_cell_keys(const float* points, int64_t n, double eps, void* workspace, int64_t* keys, int32_t* status, void* stream);
+int i2sdf_dbscan_label(const float* points, int64_t n, double eps, int32_t min_samples, const int64_t* sorted_keys, const int64_t* perm,
+                       void* workspace, int64_t* labels, uint8_t* core, int32_t* n_clusters, int32_t* status, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Sphere tracing of the SDF's zero level -- the `intersect_func` hook of RenderingLayer.forward / get_incident_radiance
  * (model/rendering/__init__.py, model/network/__init__.py).  The reference names the hook and released no implementation, so the
  * marching rule is defined HERE; tests/trace_ref.py restates it in fp32 and fp64.  csrc/mlp_trace.hip, csrc/trace_rule.h.
