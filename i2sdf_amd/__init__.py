@@ -25,7 +25,7 @@ def __getattr__(name):
         return getattr(grid, name)
     if name in ("marching_cubes", "Mesh", "face_components", "largest_component", "sample_surface", "compact",
                 "voxel_down_sample", "nearest_neighbors", "evaluate", "mesh_depth", "tsdf_fuse", "tsdf_integrate", "tsdf_extract",
-                "TsdfVolume", "refuse", "score"):
+                "TsdfVolume", "refuse", "score", "MeshBVH", "RayHits", "build_bvh", "ray_mesh_intersect", "occluded"):
         from . import mesh
         return getattr(mesh, name)
     if name in ("psnr", "ssim", "image_stats", "image_metrics", "to_frames", "interpolate_poses", "pixel_grid", "linear_to_srgb"):
@@ -37,7 +37,7 @@ def __getattr__(name):
     if name in ("KMeans", "kmeans_pp_centroid", "DBSCAN", "dbscan_seeds"):
         from . import cluster
         return getattr(cluster, name)
-    if name in ("SphereTracer", "TraceResult", "TraceResultF"):
+    if name in ("SphereTracer", "MeshTracer", "TraceResult", "TraceResultF"):
         from . import trace
         return getattr(trace, name)
     if name == "RenderEngine":

@@ -92,6 +92,9 @@ BUBBLE_MAX_K = 4096              # I2SDF_BUBBLE_MAX_K
 BUBBLE_WS_PASSES_OFFSET = 24     # I2SDF_BUBBLE_WS_PASSES_OFFSET
 KMEANS_MAX_K = 256               # I2SDF_KMEANS_MAX_K
 DBSCAN_NONFINITE, DBSCAN_CELLS = 1, 2    # I2SDF_DBSCAN_*: status bits
+RAYCAST_BAD_RAY, RAYCAST_BAD_FACE = 1, 2    # I2SDF_RAYCAST_*: status bits
+RAYCAST_CULL = {"none": 0, "back": 1}      # I2SDF_RAYCAST_CULL_*
+BVH_MAX_FACES = 1 << 28          # I2SDF_BVH_MAX_FACES
 TRACE_HIT, TRACE_MISS, TRACE_UNRESOLVED, TRACE_INSIDE = 1, 2, 3, 4      # I2SDF_TRACE_*: status of a traced ray
 TRACE_ROUTES = {"auto": 0, "stepwise": 1, "fused": 2}                   # I2SDF_TRACE_AUTO / _STEPWISE / _FUSED
 TRACE_MAX_STEPS = 1024           # I2SDF_TRACE_MAX_STEPS
@@ -271,6 +274,15 @@ SIGNATURES = {
     "i2sdf_trace_workspace_floats": (_I64, [_I64]),
     # plan, packed, cfg, cam, dirs, t_min, t_max, N, t_out, status_out, steps_out, f_trace, workspace, stream
     "i2sdf_trace_rays": (C.c_int, [_P, _P, C.POINTER(TraceCfg)] + [_P] * 4 + [_I64] + [_P] * 6),
+    "i2sdf_bvh_bytes": (_I64, [_I64]),
+    # verts, V, faces, F, bvh, keys, stream
+    "i2sdf_bvh_keys": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _P]),
+    # verts, V, faces, F, sorted_keys, bvh, stream
+    "i2sdf_bvh_build": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _P]),
+    # bvh, F, orig, dirs, t_min, t_max, n, cull, any_hit, t, face, bary, hit, status, stream
+    "i2sdf_bvh_trace": (C.c_int, [_P, _I64] + [_P] * 4 + [_I64, _I32, _I32] + [_P] * 6),
+    # verts, V, faces, F, orig, dirs, t_min, t_max, n, cull, any_hit, t, face, bary, hit, status, stream
+    "i2sdf_mesh_trace_brute": (C.c_int, [_P, _I64, _P, _I64] + [_P] * 4 + [_I64, _I32, _I32] + [_P] * 6),
     "i2sdf_light_forward": (C.c_int, [_P, _P, _P, _I64, _I64, _P, _P, _P]),
     "i2sdf_light_backward": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _P, _P, _P]),
     "i2sdf_loss_scratch_floats": (_I64, []),

@@ -39,6 +39,14 @@ convention are restated from their sources and checked against a numpy restateme
 imitated: OpenGL's 24-bit depth buffer (pyrender reads depth back through it: a relative error of about 6e-8 z / znear), open3d's
 incremental fp32 accumulation of voxel coordinates, its table for ambiguous cells, its hash map's vertex order.  The scores are the
 reference's up to those effects.
+
+Ray casting on the device (csrc/bvh.hip, csrc/tri_isect.h), the ray caster on the extracted mesh the reference's `intersect_func` hook is
+meant for, and shadow rays:
+  * build_bvh           a linear BVH over the faces (Morton keys, one torch.sort, Karras' topology, boxes fitted bottom-up);
+  * ray_mesh_intersect  the first face every ray meets, by the watertight rule of include/i2sdf.h ("Ray casting"): the smallest t, among
+                        equal t the smallest face index, the same bits through the tree and through the brute-force route;
+  * occluded            its any-hit form.
+Bitwise reproducible; tests/raycast_ref.py restates the law in numpy.
 """
 from __future__ import annotations
 
@@ -766,3 +774,134 @@ def score(pred, trgt, poses, K, H: int, W: int, far_clip: float = 5.0, threshold
     p = refuse(pred, poses, K, H, W, **dict(tsdf_kwargs))
     t = refuse(trgt, poses, K, H, W, far_clip, **dict(tsdf_kwargs))
     return evaluate(p, t, threshold=threshold, down_sample=down_sample)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Ray casting (csrc/bvh.hip; include/i2sdf.h, "Ray casting", states the law)
+class MeshBVH(NamedTuple):
+    """A linear BVH over the faces of a device mesh (build_bvh).  It refers to the mesh's tensors: they must stay as they are."""
+    verts: torch.Tensor      # (V, 3) fp32
+    faces: torch.Tensor      # (F, 3) int32
+    buffer: torch.Tensor     # i2sdf_bvh_bytes(F) uint8: header, nodes, leaves, build links
+
+
+class RayHits(NamedTuple):
+    t: torch.Tensor          # (n,) fp32, in units of the direction; t_max on a miss
+    face: torch.Tensor       # (n,) int32, -1 on a miss
+    bary: torch.Tensor       # (n, 2) fp32: the weights of the face's first and second vertex; 0 on a miss
+    hit: torch.Tensor        # (n,) bool
+    status: torch.Tensor     # (1,) int32 on the device: lib.RAYCAST_BAD_RAY | lib.RAYCAST_BAD_FACE over the call (not read back here)
+
+
+RAYCAST_ROUTES = ("auto", "bvh", "brute")
+RAYCAST_BRUTE_MAX_FACES = 256      # route="auto" on a bare mesh: at most one staged tile of faces per ray goes without a tree
+
+
+def _raycast_mesh(mesh, what):
+    if isinstance(mesh, MeshBVH):
+        return mesh
+    if not isinstance(mesh, (tuple, list)) or len(mesh) < 2:
+        raise ValueError(f"{what}: expected a Mesh, a (verts, faces) pair or a MeshBVH, got {type(mesh).__name__}")
+    for t, dt, name in ((mesh[0], torch.float32, "verts"), (mesh[1], torch.int32, "faces")):
+        if not torch.is_tensor(t) or t.dtype != dt or t.dim() != 2 or t.shape[1] != 3:
+            raise ValueError(f"{what}: {name} must be a (n, 3) {dt} tensor")
+    if mesh[0].device != mesh[1].device:
+        raise ValueError(f"{what}: verts on {mesh[0].device}, faces on {mesh[1].device}")
+    if not mesh[0].is_cuda:
+        raise L.I2SDFError(f"{what}: the mesh is on {mesh[0].device}; ray casting runs on the GPU only, there is no CPU path")
+    return mesh[0].contiguous(), mesh[1].contiguous()
+
+
+@torch.no_grad()
+def build_bvh(mesh) -> MeshBVH:
+    """The BVH of a device mesh (a Mesh or a (verts, faces) pair; F = 0 is legal): Morton keys of the face centroids, one torch.sort,
+    Karras' topology, boxes fitted bottom-up.  Enqueues only; 124 bytes per face stay allocated with the result."""
+    m = _raycast_mesh(mesh, "build_bvh")
+    if isinstance(m, MeshBVH):
+        return m
+    verts, faces = m
+    lib = L.load()
+    V, F, dev = verts.shape[0], faces.shape[0], verts.device
+    with torch.cuda.device(dev):
+        nbytes = int(lib.i2sdf_bvh_bytes(F))
+        if nbytes <= 0:
+            raise ValueError(f"build_bvh: {F} faces are more than the {L.BVH_MAX_FACES} a tree holds")
+        buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        keys = torch.empty(F, dtype=torch.int64, device=dev)
+        st = L.stream_ptr()
+        L.check(lib.i2sdf_bvh_keys(L.ptr(verts), V, L.ptr(faces), F, L.ptr(buf), L.ptr(keys), st), "i2sdf_bvh_keys")
+        skeys = torch.sort(keys, stable=True)[0]              # (unique keys; the face index rides in their low word)
+        L.check(lib.i2sdf_bvh_build(L.ptr(verts), V, L.ptr(faces), F, L.ptr(skeys), L.ptr(buf), st), "i2sdf_bvh_build")
+    return MeshBVH(verts, faces, buf)
+
+
+def _ray_args(origins, dirs, t_min, t_max, dev, what):
+    for name, t in (("origins", origins), ("dirs", dirs)):
+        if not torch.is_tensor(t) or t.dim() != 2 or t.shape[1] != 3 or not t.dtype.is_floating_point:
+            raise ValueError(f"{what}: {name} must be a (n, 3) floating-point tensor")
+    if dirs.shape != origins.shape:
+        raise ValueError(f"{what}: origins {tuple(origins.shape)} and dirs {tuple(dirs.shape)} differ")
+    n = origins.shape[0]
+    if origins.device != dev or dirs.device != dev:
+        raise ValueError(f"{what}: the rays are on {origins.device} / {dirs.device}, the mesh on {dev}")
+    bounds = []
+    for name, b in (("t_min", t_min), ("t_max", t_max)):
+        if torch.is_tensor(b):
+            if tuple(b.shape) != (n,) or not b.dtype.is_floating_point or b.device != dev:
+                raise ValueError(f"{what}: {name} must be a number or a ({n},) floating-point tensor on {dev}")
+            bounds.append(b.detach().to(torch.float32).contiguous())
+        elif isinstance(b, (int, float)) and not isinstance(b, bool):
+            bounds.append(torch.full((n,), float(b), dtype=torch.float32, device=dev))
+        else:
+            raise TypeError(f"{what}: {name} must be a number or an ({n},) tensor, got {type(b).__name__}")
+    c = lambda t: t.detach().to(torch.float32).contiguous()
+    return c(origins), c(dirs), bounds[0], bounds[1]
+
+
+@torch.no_grad()
+def ray_mesh_intersect(bvh_or_mesh, origins, dirs, t_min=0.0, t_max=float("inf"), cull: str = "none", any_hit: bool = False,
+                       route: str = "auto") -> RayHits:
+    """The first face every ray o + t d meets with t_min < t <= t_max (numbers or per-ray tensors), by the watertight rule of
+    include/i2sdf.h: the smallest t, among equal t the smallest face index -- the same bits by every route.  Directions need not be
+    unit; t is in units of `dirs`.  cull="back" ignores faces whose right-hand normal points along the ray (mesh_depth's back faces).
+    any_hit=True fills only `hit` (t, face, bary are None); it equals the closest-hit flag.
+    route: "bvh" (a bare mesh gets its tree built first), "brute" (every ray against every face: the reference route), "auto" (the
+    tree when one is given or the mesh has more than RAYCAST_BRUTE_MAX_FACES faces).  Enqueues only."""
+    what = "ray_mesh_intersect"
+    if cull not in L.RAYCAST_CULL:
+        raise ValueError(f"{what}: cull = {cull!r} is none of {sorted(L.RAYCAST_CULL)}")
+    if route not in RAYCAST_ROUTES:
+        raise ValueError(f"{what}: route = {route!r} is none of {list(RAYCAST_ROUTES)}")
+    m = _raycast_mesh(bvh_or_mesh, what)
+    verts, faces = m[0], m[1]
+    dev = verts.device
+    o, d, t0, t1 = _ray_args(origins, dirs, t_min, t_max, dev, what)
+    if not verts.is_cuda:
+        raise L.I2SDFError(f"{what}: the mesh is on {dev}; ray casting runs on the GPU only, there is no CPU path")
+    lib = L.load()
+    n, V, F = o.shape[0], verts.shape[0], faces.shape[0]
+    if route == "auto":
+        route = "bvh" if isinstance(m, MeshBVH) or F > RAYCAST_BRUTE_MAX_FACES else "brute"
+    if route == "bvh" and not isinstance(m, MeshBVH):
+        m = build_bvh(m)
+    with torch.cuda.device(dev):
+        hit = torch.empty(n, dtype=torch.uint8, device=dev)
+        status = torch.empty(1, dtype=torch.int32, device=dev)
+        t = face = bary = None
+        if not any_hit:
+            t = torch.empty(n, dtype=torch.float32, device=dev)
+            face = torch.empty(n, dtype=torch.int32, device=dev)
+            bary = torch.empty(n, 2, dtype=torch.float32, device=dev)
+        out = (L.ptr(t), L.ptr(face), L.ptr(bary), L.ptr(hit), L.ptr(status), L.stream_ptr())
+        flags = (n, L.RAYCAST_CULL[cull], int(bool(any_hit)))
+        if route == "bvh":
+            L.check(lib.i2sdf_bvh_trace(L.ptr(m.buffer), F, L.ptr(o), L.ptr(d), L.ptr(t0), L.ptr(t1), *flags, *out), "i2sdf_bvh_trace")
+        else:
+            L.check(lib.i2sdf_mesh_trace_brute(L.ptr(verts), V, L.ptr(faces), F, L.ptr(o), L.ptr(d), L.ptr(t0), L.ptr(t1), *flags, *out),
+                    "i2sdf_mesh_trace_brute")
+    return RayHits(t, face, bary, hit.view(torch.bool), status)
+
+
+def occluded(bvh_or_mesh, origins, dirs, t_min=0.0, t_max=float("inf"), cull: str = "none", route: str = "auto") -> torch.Tensor:
+    """(n,) bool: is anything met with t_min < t <= t_max -- a shadow ray.  ray_mesh_intersect(..., any_hit=True).hit."""
+    return ray_mesh_intersect(bvh_or_mesh, origins, dirs, t_min, t_max, cull, True, route).hit

@@ -555,14 +555,18 @@ class I2SDFNetwork(nn.Module):
         `intersect_func` (the reference's hook for a ray caster): None, or a tracer of THIS module (`self.sphere_tracer(...)`,
         i2sdf_amd.SphereTracer) -- the result is then `rgb_values` of `render_surface` for those rays: the radiance net at the first
         surface hit, zero where the ray hits nothing, a few tens of SDF evaluations per ray instead of the sampler's several hundred.
-        Anything else -- a callable, a tracer bound to another module -- is refused: there is no external ray caster to call."""
+        With this module's `self.mesh_tracer(mesh)` (i2sdf_amd.MeshTracer) the hit is found on a triangle mesh by the BVH ray caster
+        (no network pass) and the result is `rgb_values` of `render_surface(..., intersect_func=tracer)`.
+        Anything else -- a callable, a tracer of either kind bound to another module -- is refused: a foreign ray caster is not called."""
         if intersect_func is not None:
-            from .trace import SphereTracer, _rays_input
+            from .trace import MeshTracer, SphereTracer, _rays_input
             if isinstance(intersect_func, SphereTracer) and intersect_func.net is self:
                 return self.render_surface(_rays_input(pts, dirs, "get_incident_radiance"), **intersect_func.kw)["rgb_values"]
+            if isinstance(intersect_func, MeshTracer) and intersect_func.net is self:
+                return self.render_surface(_rays_input(pts, dirs, "get_incident_radiance"), intersect_func=intersect_func)["rgb_values"]
             raise NotImplementedError("get_incident_radiance: intersect_func is not supported unless it is this module's own sphere_tracer() "
-                                      "(otherwise the secondary rays are rendered by the volume renderer itself, there is no external ray "
-                                      "caster to call)")
+                                      "or mesh_tracer() (otherwise the secondary rays are rendered by the volume renderer itself; a foreign "
+                                      "ray caster is not called)")
         if pts.dim() != 2 or pts.shape[1] != 3 or dirs.shape != pts.shape:
             raise ValueError(f"get_incident_radiance: pts {tuple(pts.shape)} and dirs {tuple(dirs.shape)} must both be (n, 3)")
         pts, dirs = pts.detach().to(torch.float32).contiguous(), dirs.detach().to(torch.float32).contiguous()
@@ -581,6 +585,12 @@ class I2SDFNetwork(nn.Module):
         RenderEngine.trace_rays."""
         from .trace import SphereTracer
         return SphereTracer(self, **kw)
+
+    def mesh_tracer(self, mesh, **kw):
+        """An `intersect_func` bound to this module that finds its hits on `mesh` (a Mesh, a (verts, faces) pair or a MeshBVH) with the
+        BVH ray caster (i2sdf_amd.MeshTracer); kw: t_min, t_max, cull."""
+        from .trace import MeshTracer
+        return MeshTracer(self, mesh, **kw)
 
     @staticmethod
     def _surface_rays(input, who):
@@ -608,7 +618,20 @@ class I2SDFNetwork(nn.Module):
 
     def _surface(self, input, with_rgb, split_n_pixels, who, kw):
         from . import lib as L_
-        from .trace import check_trace_cfg
+        from .trace import MeshTracer, SphereTracer, check_trace_cfg
+        mesh_tracer = None
+        if "intersect_func" in kw:
+            kw = dict(kw)
+            f = kw.pop("intersect_func")
+            if isinstance(f, MeshTracer) and f.net is self:
+                if kw:
+                    raise TypeError(f"{who}: with a mesh tracer the keywords {sorted(kw)} have no meaning (its bounds and culling are its own)")
+                mesh_tracer = f
+            elif isinstance(f, SphereTracer) and f.net is self:
+                kw = {**f.kw, **kw}
+            elif f is not None:
+                raise NotImplementedError(f"{who}: intersect_func is not supported unless it is this module's own sphere_tracer() or "
+                                          "mesh_tracer()")
         check_trace_cfg(**{k: v for k, v in kw.items() if k in ("eps", "max_steps", "step_scale", "route")})
         if split_n_pixels is not None and (isinstance(split_n_pixels, bool) or not isinstance(split_n_pixels, int) or split_n_pixels < 1):
             raise ValueError(f"{who}: split_n_pixels = {split_n_pixels!r} must be a positive integer or None")
@@ -631,10 +654,17 @@ class I2SDFNetwork(nn.Module):
                     hi = min(lo + step, N)
                     b = {k: (v[lo:hi] if isinstance(v, torch.Tensor) and v.dim() == 1 and v.shape[0] == N else v) for k, v in bounds.items()}
                     c, d = cam[lo:hi], dirs[lo:hi]
-                    tr = eng.trace_rays(c, d, **b, **tkw)
                     n = hi - lo
-                    hit = tr.status == L_.TRACE_HIT
-                    o = {"status": tr.status, "hit": hit, "t": tr.t, "depth_values": tr.t / dnorm[lo:hi]}
+                    if mesh_tracer is not None:
+                        rh = mesh_tracer.intersect(cam, dirs, lo, hi)
+                        hit, t = rh.hit, rh.t
+                        status = torch.where(hit, L_.TRACE_HIT, L_.TRACE_MISS).to(torch.int32)
+                        t_at = torch.where(hit, t, torch.zeros((), dtype=torch.float32, device=dev))      # (a miss may sit at t = inf)
+                        o = {"status": status, "hit": hit, "t": t, "depth_values": t / dnorm[lo:hi], "face": rh.face, "bary": rh.bary}
+                    else:
+                        tr = eng.trace_rays(c, d, **b, **tkw)
+                        hit, t_at = tr.status == L_.TRACE_HIT, tr.t
+                        o = {"status": tr.status, "hit": hit, "t": tr.t, "depth_values": tr.t / dnorm[lo:hi]}
                     zero3 = torch.zeros(n, 3, dtype=torch.float32, device=dev)
                     if n == 0:
                         o.update(points=zero3, normal_map=zero3, feature_vectors=torch.zeros(0, self.feature_vector_size, device=dev))
@@ -642,20 +672,27 @@ class I2SDFNetwork(nn.Module):
                             o["rgb_values"] = zero3
                         parts.append(o)
                         continue
-                    h3 = hit.unsqueeze(1)
-                    # value, gradient and features at the point where the march stopped
-                    fw = eng.sdf_forward_grad(rays=(c, d, tr.t.reshape(n, 1), 1), want_grad=True, save=False)
-                    # (fma(t, d, o) as the kernels form it, include/i2sdf.h: exact product and one rounding of the sum through fp64)
-                    o["points"] = torch.where(h3, (c.double() + tr.t.double().unsqueeze(1) * d.double()).float(), zero3)
-                    o["normal_map"] = torch.where(h3, torch.nn.functional.normalize(fw["grad"], dim=1), zero3)
-                    o["feature_vectors"] = torch.where(h3, fw["feat"][:n], torch.zeros((), dtype=torch.float32, device=dev))
-                    if with_rgb:
-                        rgb, _, _ = eng.rgb_forward(d, 1, fw["feat"], n, save=False, fw=fw)
-                        o["rgb_values"] = torch.where(h3, rgb, zero3)
+                    self._surface_tail(eng, o, c, d, t_at, hit, with_rgb)
                     parts.append(o)
                 return parts[0] if len(parts) == 1 else {k: torch.cat([p_[k] for p_ in parts], 0) for k in parts[0]}
         finally:
             self.train(was_training)
+
+    def _surface_tail(self, eng, o, c, d, t, hit, with_rgb):
+        """What a surface view holds beside its depths, whichever tracer found them: value, gradient and features at the depth t of
+        every ray (c, d), and the radiance net there; exact zeros on the rows without a hit.  Fills `o`."""
+        n, dev = c.shape[0], c.device
+        zero3 = torch.zeros(n, 3, dtype=torch.float32, device=dev)
+        h3 = hit.unsqueeze(1)
+        # value, gradient and features at the point where the march stopped
+        fw = eng.sdf_forward_grad(rays=(c, d, t.reshape(n, 1), 1), want_grad=True, save=False)
+        # (fma(t, d, o) as the kernels form it, include/i2sdf.h: exact product and one rounding of the sum through fp64)
+        o["points"] = torch.where(h3, (c.double() + t.double().unsqueeze(1) * d.double()).float(), zero3)
+        o["normal_map"] = torch.where(h3, torch.nn.functional.normalize(fw["grad"], dim=1), zero3)
+        o["feature_vectors"] = torch.where(h3, fw["feat"][:n], torch.zeros((), dtype=torch.float32, device=dev))
+        if with_rgb:
+            rgb, _, _ = eng.rgb_forward(d, 1, fw["feat"], n, save=False, fw=fw)
+            o["rgb_values"] = torch.where(h3, rgb, zero3)
 
     def trace_surface(self, input, **kw):
         """The first intersection of every ray of `input` with the zero level of the SDF, by sphere tracing (RenderEngine.trace_rays; kw are
@@ -665,7 +702,10 @@ class I2SDFNetwork(nn.Module):
           status (N,) int32 (i2sdf_amd.trace.HIT / MISS / UNRESOLVED / INSIDE), hit (N,) bool = status == HIT, t (N,) the depth along the
           unit direction, depth_values (N,) = t / dnorm (the reference's depth convention), points (N, 3) = cam_loc + t dirs,
           normal_map (N, 3) the normalised d sdf/dx there, feature_vectors (N, F).  points, normal_map and feature_vectors are exact zeros
-          on the rows without a hit; t is where the march stopped (t_max for a MISS)."""
+          on the rows without a hit; t is where the march stopped (t_max for a MISS).
+        `intersect_func=` this module's mesh_tracer(...): the hit is found on the tracer's mesh by the BVH ray caster instead (no other
+        keyword then); status is HIT or MISS, the outputs gain face (N,) int32 and bary (N, 2), everything else is formed at the mesh's t
+        exactly as above.  This module's sphere_tracer(...) there stands for its keywords."""
         return self._surface(input, False, None, "trace_surface", kw)
 
     def render_surface(self, input, split_n_pixels=None, **kw):

@@ -84,3 +84,35 @@ def _rays_input(pts, dirs, who):
         raise ValueError(f"{who}: pts {tuple(getattr(pts, 'shape', ()))} and dirs {tuple(getattr(dirs, 'shape', ()))} must both be (n, 3)")
     pts, dirs = pts.detach().to(torch.float32).contiguous(), dirs.detach().to(torch.float32).contiguous()
     return {"uv": pts, "rays": {"cam_loc": pts, "dirs": dirs, "dnorm": torch.ones(pts.shape[0], dtype=torch.float32, device=pts.device)}}
+
+
+class MeshTracer:
+    """An `intersect_func` that finds the hit on a triangle MESH (i2sdf_amd.ray_mesh_intersect: a BVH trace, no network pass) instead of
+    marching the network: bound to ONE module, it makes that module answer a ray with the radiance net at the mesh hit -- one SDF +
+    radiance pass at fma(t, d, o), the tail sphere tracing ends with.  Made by `net.mesh_tracer(mesh_or_bvh, t_min=0.0, t_max=None,
+    cull="none")`; a bare mesh gets its tree built once, here.  t_max None: unbounded.  Called directly, tracer(pts, dirs) returns
+    net.trace_surface of those rays.  The mesh is a snapshot: it does not follow the network's weights."""
+
+    def __init__(self, net, mesh_or_bvh, t_min=0.0, t_max=None, cull="none"):
+        from . import mesh as M
+        if cull not in L.RAYCAST_CULL:
+            raise ValueError(f"mesh_tracer: cull = {cull!r} is none of {sorted(L.RAYCAST_CULL)}")
+        for name, b in (("t_min", t_min), ("t_max", t_max)):
+            if b is None and name == "t_max":
+                continue
+            if isinstance(b, bool) or not isinstance(b, (int, float, torch.Tensor)):
+                raise TypeError(f"mesh_tracer: {name} must be a number or a per-ray tensor, got {type(b).__name__}")
+        self.net = net
+        self.bvh = M.build_bvh(mesh_or_bvh)
+        self.t_min, self.t_max, self.cull = t_min, (math.inf if t_max is None else t_max), cull
+
+    def intersect(self, cam, dirs, lo=None, hi=None):
+        """RayHits of rays lo..hi of (cam, dirs); per-ray bounds are cut to the same rows"""
+        from . import mesh as M
+        N = cam.shape[0]
+        cut = lambda b: b[lo:hi] if isinstance(b, torch.Tensor) and b.dim() == 1 and b.shape[0] == N and lo is not None else b
+        c, d = (cam, dirs) if lo is None else (cam[lo:hi], dirs[lo:hi])
+        return M.ray_mesh_intersect(self.bvh, c, d, cut(self.t_min), cut(self.t_max), self.cull, False, "bvh")
+
+    def __call__(self, pts, dirs):
+        return self.net.trace_surface(_rays_input(pts, dirs, "mesh_tracer"), intersect_func=self)

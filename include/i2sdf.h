@@ -1252,6 +1252,92 @@ int i2sdf_trace_rays(const i2sdf_plan* plan, const float* packed, const i2sdf_tr
                      const float* t_min, const float* t_max, int64_t N, float* t_out, int32_t* status_out, int32_t* steps_out,
                      float* f_trace, float* workspace, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Ray casting against a triangle mesh -- the external ray caster the `intersect_func` hook of RenderingLayer.forward /
+ * get_incident_radiance is meant for, on the mesh the library extracts itself; also occlusion queries.  csrc/bvh.hip, csrc/tri_isect.h.
+ * No plan.  Every call only enqueues on `stream`: no allocation, no synchronisation, no host read.  tests/raycast_ref.py restates the
+ * rule, the keys and the topology in numpy.
+ *
+ * The law.  verts (V, 3) fp32, faces (F, 3) int32, rays o = orig[r], d = dirs[r] (any length, t is in units of d), t_min[r], t_max[r].
+ *   Ray.  kz = the axis of the largest |d| (the lowest such axis); kx = kz + 1, ky = kx + 1 (mod 3), swapped when d[kz] < 0;
+ *         Sx = d[kx] / d[kz], Sy = d[ky] / d[kz], Sz = 1 / d[kz].  A ray with a non-finite component of o or d, with d = 0, with a
+ *         non-finite Sz, or with a NaN bound hits nothing and sets I2SDF_RAYCAST_BAD_RAY.
+ *   Face (A, B, C), per vertex P:  Pkz = P[kz] - o[kz];  Px = (P[kx] - o[kx]) - Sx * Pkz;  Py = (P[ky] - o[ky]) - Sy * Pkz.
+ *         U = Cx * By - Cy * Bx;  V = Ax * Cy - Ay * Cx;  W = Bx * Ay - By * Ax.
+ *         If U == 0 or V == 0 or W == 0: all three are formed again from the fp64 images of the six sheared coordinates (products
+ *         exact, one rounding of the difference) and rounded to fp32.
+ *         Reject if one of U, V, W is < 0 and one is > 0.  det = (U + V) + W; reject if det == 0.
+ *         cull: det < 0 is a BACK face -- its right-hand normal (B - A) x (C - A) points along the ray -- rejected under
+ *         I2SDF_RAYCAST_CULL_BACK.  These are the faces i2sdf_mesh_depth calls back faces (its own determinant is positive there).
+ *         Pz = Sz * Pkz;  T = (U * Az + V * Bz) + W * Cz;  t = T / det;  u = U / det, v = V / det (the weights of A and of B).
+ *         The face counts iff t_min < t <= t_max.
+ *         Every operation above is ONE fp32 operation, rounded to nearest, in the order written, none contracted into an FMA: a*b - c*d
+ *         is the exact negative of c*d - a*b only without one, and that is what makes the two faces at a shared edge see exactly
+ *         negated edge functions: a ray cannot slip between them (Woop, Benthin, Wald: Watertight Ray/Triangle Intersection, JCGT 2013).
+ *   Faces that are never hit: an index outside [0, V) or a non-finite vertex (sets I2SDF_RAYCAST_BAD_FACE in every trace of that
+ *         mesh, whatever the rays); two equal vertices (the zero-area faces marching cubes emits: their sheared image is degenerate,
+ *         so U + V + W is exactly 0 and non-mixed signs mean U = V = W = 0).
+ *   Result per ray: the smallest t among the faces that count; among equal t the smallest face index.  An order-free function of the
+ *         inputs, so bitwise reproducible and the same by every route.  A miss returns face = -1, t = t_max, u = v = 0.
+ *         any_hit: only hit[r] is written; it IS the closest-hit flag (the search may stop at the first face that counts).
+ *   *status: the OR of the two bits over the call.
+ *
+ * The tree (i2sdf_bvh_keys -> the caller's sort -> i2sdf_bvh_build), a linear BVH, one face per leaf.
+ *   Keys.  lo, hi = per-axis min / max of the vertices of the faces that can be hit (a device reduction).  Per axis, in fp64:
+ *         c = ((a + b) + c') / 3;  q = hi > lo ? clamp(floor(((c - lo) / (hi - lo)) * 1024), 0, 1023) : 0.  code = the 30-bit Morton
+ *         interleave of (qx, qy, qz), x highest; a face that is never hit for its indices or vertices takes code 2^30.
+ *         key = code << 32 | face: unique, and the face index rides in the low word.  The CALLER sorts the keys ascending (torch.sort).
+ *   Topology.  Karras (Maximizing Parallelism in the Construction of BVHs, Octrees, and k-d Trees, HPG 2012): internal node i of
+ *         F - 1, node 0 the root, delta(i, j) = the number of leading bits sorted keys i and j share (-1 outside the array).
+ *   Boxes.  The exact fp32 min / max of the vertex coordinates below a child (`b < a ? b : a` in the order A, B, C, then slot 0, slot 1),
+ *         no padding; the empty box (+inf, -inf) below faces that are never hit.  Fitted bottom-up, one arrival counter per node.
+ *   Records.  Internal node, 64 bytes: lo0[3], hi0[3], lo1[3], hi1[3], child[2] (>= 0: internal node; < 0: leaf ~child), 8 unused.
+ *         Leaf, 48 bytes, in sorted order: A, B, C, face (-1: never hit), 8 unused.  Buffer: 256 header | 64 F nodes | 48 F leaves |
+ *         3 x 4 F (parent links, arrival counters) = 124 bytes per face: i2sdf_bvh_bytes(F), a multiple of 16, monotone, at most
+ *         124 F + 304; 0 for F < 0 or F > I2SDF_BVH_MAX_FACES = 2^28 (node indices, their complements and `node << 1 | slot` parent
+ *         links stay inside int32, and the 33 GB of such a tree still fit one device beside its mesh).  F = 0 is a valid empty tree
+ *         (every ray misses), F = 1 a single leaf, F = 2 one node.
+ *
+ * The trace: one lane per ray, the nearer child first, the other on a per-lane stack of 64 slots in LDS (the key has 63 significant
+ * bits, so the tree is at most 63 deep).  A child is skipped only if box_may_hit (csrc/tri_isect.h) is false, and that is conservative
+ * with respect to the rule itself, not to the geometry:
+ *   (x, y)  The signs of U, V, W are exact signs of the edge functions of the COMPUTED sheared vertices: rounding is monotone, so a
+ *         non-zero fp32 difference of two rounded products has the sign of the exact one, and a zero is recomputed exactly.  So a face
+ *         counts only if the origin of the sheared plane lies in the closed triangle of its computed (Px, Py).  Px is a monotone
+ *         function of P[kx] and of P[kz] (subtraction, multiplication by a constant and rounding all are), so over a box it lies
+ *         between its values at two corners, formed with the SAME operations: x_min = (lo[kx] - o[kx]) - max(Sx zl, Sx zh),
+ *         x_max = (hi[kx] - o[kx]) - min(Sx zl, Sx zh), zl = lo[kz] - o[kz], zh = hi[kz] - o[kz].  x_min > 0 or x_max < 0 puts all
+ *         three Px strictly on one side of 0: the origin is outside, the signs are mixed (or the image degenerate): no ulp is needed.
+ *   (t)   With U, V, W of one sign, T = sum U_i Pz_i (1 + a_i), |a_i| <= 3 e, det = sum U_i (1 + b_i), |b_i| <= 2 e, e = 2^-24, and
+ *         t = (T / det)(1 + c): t is a convex combination of Pz_i (1 + a_i)(1 + c) / (1 + b_i), so it lies in the hull of the three
+ *         Pz_i widened by a relative 6 e + O(e^2) < 2^-21.  Pz = Sz * (P[kz] - o[kz]) is monotone in P[kz]: the hull lies inside
+ *         [Sz zl, Sz zh] formed with the same operations.  The test widens both ends by 2^-20 of their magnitude (twice the bound:
+ *         the widening is itself rounded) and skips if near > best t or far < t_min; near == best t is ENTERED, since a tie may go
+ *         to a smaller face index.  (The bound assumes no product underflows; coordinates of ordinary magnitude do not.)
+ *   NaN   Sx, Sy, Sz are finite (|Sx|, |Sy| <= 1) and no division occurs per box, so a zero direction component or an origin on a box
+ *         plane creates no 0 * inf; an overflowing difference can, and every skip is written so that a NaN operand does NOT skip.
+ * i2sdf_mesh_trace_brute: every ray against every face through the same inline function: the reference route and the small-mesh route.
+ *
+ *   orig, dirs (n, 3); t_min, t_max (n); t (n) fp32, face (n) int32, bary (n, 2) fp32 (NULL allowed with any_hit), hit (n) uint8,
+ *   status (1) int32.  0 <= n < 2^31; n = 0 still reports the face bit.  bvh: i2sdf_bvh_bytes(F) bytes, 16-byte aligned; the SAME
+ *   verts, faces, F and buffer through keys, build and every trace; sorted_keys (F) int64.
+ * Refused with I2SDF_EINVAL before any launch: a NULL or misaligned pointer (stream excepted; mesh pointers when F = 0 and ray
+ *   pointers when n = 0 too), F outside 0..I2SDF_BVH_MAX_FACES, V outside 0..2^31-1, n outside the range, cull or any_hit not 0 / 1.
+ * ---------------------------------------------------------------------------------------------- */
+#define I2SDF_RAYCAST_BAD_RAY 1       /* status bit 0 */
+#define I2SDF_RAYCAST_BAD_FACE 2      /* status bit 1 */
+#define I2SDF_RAYCAST_CULL_NONE 0
+#define I2SDF_RAYCAST_CULL_BACK 1
+#define I2SDF_BVH_MAX_FACES 268435456
+int64_t i2sdf_bvh_bytes(int64_t F);
+int i2sdf_bvh_keys(const float* verts, int64_t V, const int32_t* faces, int64_t F, void* bvh, int64_t* keys, void* stream);
+int i2sdf_bvh_build(const float* verts, int64_t V, const int32_t* faces, int64_t F, const int64_t* sorted_keys, void* bvh, void* stream);
+int i2sdf_bvh_trace(const void* bvh, int64_t F, const float* orig, const float* dirs, const float* t_min, const float* t_max, int64_t n,
+                    int32_t cull, int32_t any_hit, float* t, int32_t* face, float* bary, uint8_t* hit, int32_t* status, void* stream);
+int i2sdf_mesh_trace_brute(const float* verts, int64_t V, const int32_t* faces, int64_t F, const float* orig, const float* dirs,
+                           const float* t_min, const float* t_max, int64_t n, int32_t cull, int32_t any_hit, float* t, int32_t* face,
+                           float* bary, uint8_t* hit, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
