@@ -27,6 +27,7 @@
 #include "../../include/i2sdf.h"
 #include "blockops.h"
 #include "tri_isect.h"
+#include "bvh_tree.h"
 
 #pragma clang fp contract(off)
 
@@ -35,67 +36,13 @@ int i2sdf_hip_check(hipError_t e, const char* what);
 namespace {
 
 using namespace i2sdf_blockops;
+using namespace i2sdf_bvh;
 using i2sdf::RayShear;
 
 constexpr int BV_THREADS = 256, BV_MAX_BLOCKS = 4096;
 constexpr int TR_THREADS = 128, TR_STACK = 64;
 constexpr int BR_THREADS = 256;
-constexpr int64_t BVH_HEADER = 256;
 constexpr uint32_t BAD_CODE = 1u << 30;
-
-struct Header {
-  uint32_t bounds[8];          // [0..2] minima, [4..6] maxima of the valid faces' vertices (order-preserving images)
-  int32_t flags;               // I2SDF_RAYCAST_BAD_FACE, or 0
-  int32_t pad[3];
-};
-
-struct __attribute__((aligned(16))) Node {      // 64 bytes
-  float lo0[3], hi0[3], lo1[3], hi1[3];
-  int32_t child[2];            // >= 0: internal node; < 0: leaf ~child
-  int32_t pad[2];
-};
-struct __attribute__((aligned(16))) Leaf {      // 48 bytes
-  float v[9];
-  int32_t face;                // -1: never hit
-  int32_t pad[2];
-};
-static_assert(sizeof(Node) == 64 && sizeof(Leaf) == 48, "record sizes are part of include/i2sdf.h");
-
-struct Layout { int64_t nodes, leaves, nparent, lparent, counter, bytes; };
-
-inline bool size_ok(int64_t F) { return F >= 0 && F <= I2SDF_BVH_MAX_FACES; }
-inline Layout layout(int64_t F) {
-  Layout w;
-  int64_t o = BVH_HEADER;
-  w.nodes = o;   o += 64 * F;                      // F - 1 are used
-  w.leaves = o;  o += 48 * F;
-  w.nparent = o; o = align16(o + 4 * F);           // parent << 1 | slot of internal node i (node 0: unused)
-  w.lparent = o; o = align16(o + 4 * F);           // the same of leaf j
-  w.counter = o; o = align16(o + 4 * F);           // arrivals at internal node i
-  w.bytes = o;
-  return w;
-}
-
-__device__ __forceinline__ uint32_t f_enc(float f) { const uint32_t b = __float_as_uint(f); return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }
-__device__ __forceinline__ float f_dec(uint32_t e) { return __uint_as_float((e & 0x80000000u) ? (e & 0x7fffffffu) : ~e); }
-__device__ __forceinline__ float min_f(float a, float b) { return b < a ? b : a; }
-__device__ __forceinline__ float max_f(float a, float b) { return b > a ? b : a; }
-
-// the nine coordinates of face f, or false for a face that is never hit
-__device__ __forceinline__ bool load_face(const float* __restrict__ verts, int64_t V, const int32_t* __restrict__ faces, int64_t f, float v[9]) {
-  const int32_t i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
-  if (i0 < 0 || i1 < 0 || i2 < 0 || i0 >= V || i1 >= V || i2 >= V) return false;
-  bool ok = true;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    v[k] = verts[3 * (int64_t)i0 + k];
-    v[3 + k] = verts[3 * (int64_t)i1 + k];
-    v[6 + k] = verts[3 * (int64_t)i2 + k];
-  }
-#pragma unroll
-  for (int k = 0; k < 9; ++k) ok = ok && i2sdf::finite_f(v[k]);
-  return ok;
-}
 
 // ---------------------------------------------------------------------------------------------- bounds and keys
 __global__ __launch_bounds__(BV_THREADS) void bvh_bounds_kernel(const float* __restrict__ verts, int64_t V, const int32_t* __restrict__ faces,
@@ -402,10 +349,6 @@ __global__ __launch_bounds__(BR_THREADS) void mesh_trace_brute_kernel(const floa
 }
 
 inline unsigned face_blocks(int64_t F) { return blocks(F, BV_THREADS, BV_MAX_BLOCKS); }
-inline bool aligned(const void* p, uintptr_t a) { return p && ((uintptr_t)p & (a - 1)) == 0; }
-inline bool mesh_ok(const float* verts, int64_t V, const int32_t* faces, int64_t F) {
-  return size_ok(F) && V >= 0 && V <= INT32_MAX && (F == 0 || (aligned(verts, 4) && aligned(faces, 4)));
-}
 inline bool rays_ok(const float* orig, const float* dirs, const float* t_min, const float* t_max, int64_t n, int32_t cull, int32_t any_hit,
                     const float* t, const int32_t* face, const float* bary, const uint8_t* hit, const int32_t* status) {
   if (n < 0 || n > INT32_MAX || (cull != I2SDF_RAYCAST_CULL_NONE && cull != I2SDF_RAYCAST_CULL_BACK) || (any_hit != 0 && any_hit != 1)) return false;

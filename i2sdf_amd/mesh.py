@@ -47,6 +47,15 @@ meant for, and shadow rays:
                         equal t the smallest face index, the same bits through the tree and through the brute-force route;
   * occluded            its any-hit form.
 Bitwise reproducible; tests/raycast_ref.py restates the law in numpy.
+
+Point-to-mesh queries on the device (csrc/closest.hip, csrc/tri_closest.h), what trimesh's `proximity` and open3d's
+compute_closest_points / compute_signed_distance answer on the host, through the same tree:
+  * closest_point       the closest point of the surface, its distance, face, weights and feature, by the fp64 rule of include/i2sdf.h
+                        ("Closest point"): the smallest squared distance, among equal ones the smallest face index;
+  * pseudonormals       the angle-weighted vertex and edge normals of the sign test (Baerentzen and Aanaes);
+  * signed_distance     the distance with that sign: the quantity the implicit network approximates;
+  * surface_scores      the five numbers of evaluate from surface samples to the other mesh's SURFACE, not to a vertex set.
+Bitwise reproducible; tests/closest_ref.py restates the law in numpy.
 """
 from __future__ import annotations
 
@@ -797,7 +806,7 @@ RAYCAST_ROUTES = ("auto", "bvh", "brute")
 RAYCAST_BRUTE_MAX_FACES = 256      # route="auto" on a bare mesh: at most one staged tile of faces per ray goes without a tree
 
 
-def _raycast_mesh(mesh, what):
+def _raycast_mesh(mesh, what, cpu_ok=False):
     if isinstance(mesh, MeshBVH):
         return mesh
     if not isinstance(mesh, (tuple, list)) or len(mesh) < 2:
@@ -807,7 +816,7 @@ def _raycast_mesh(mesh, what):
             raise ValueError(f"{what}: {name} must be a (n, 3) {dt} tensor")
     if mesh[0].device != mesh[1].device:
         raise ValueError(f"{what}: verts on {mesh[0].device}, faces on {mesh[1].device}")
-    if not mesh[0].is_cuda:
+    if not mesh[0].is_cuda and not cpu_ok:
         raise L.I2SDFError(f"{what}: the mesh is on {mesh[0].device}; ray casting runs on the GPU only, there is no CPU path")
     return mesh[0].contiguous(), mesh[1].contiguous()
 
@@ -905,3 +914,178 @@ def ray_mesh_intersect(bvh_or_mesh, origins, dirs, t_min=0.0, t_max=float("inf")
 def occluded(bvh_or_mesh, origins, dirs, t_min=0.0, t_max=float("inf"), cull: str = "none", route: str = "auto") -> torch.Tensor:
     """(n,) bool: is anything met with t_min < t <= t_max -- a shadow ray.  ray_mesh_intersect(..., any_hit=True).hit."""
     return ray_mesh_intersect(bvh_or_mesh, origins, dirs, t_min, t_max, cull, True, route).hit
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Closest point (csrc/closest.hip; include/i2sdf.h, "Closest point", states the law)
+class ClosestPoints(NamedTuple):
+    dist: torch.Tensor       # (n,) fp32; +inf on a miss
+    point: torch.Tensor      # (n, 3) fp32: the closest point of the mesh; 0 on a miss
+    face: torch.Tensor       # (n,) int32, -1 on a miss
+    bary: torch.Tensor       # (n, 2) fp32: the weights of the face's first and second vertex; 0 on a miss
+    feature: torch.Tensor    # (n,) uint8: lib.CLOSEST_FEATURES; 0 on a miss
+    sdist: torch.Tensor      # (n,) fp32: dist with the pseudonormal sign (negative inside); None without normals
+    status: torch.Tensor     # (1,) int32 on the device: lib.CLOSEST_BAD_POINT | lib.CLOSEST_BAD_FACE over the call (not read back here)
+
+
+class MeshNormals(NamedTuple):
+    """The angle-weighted pseudonormals of a mesh (pseudonormals): not normalised, only their direction is used."""
+    vertex: torch.Tensor     # (V, 3) fp32
+    edge: torch.Tensor       # (F, 3, 3) fp32: [face][AB, BC, CA]
+
+
+# route="auto" on a bare mesh.  profiles/closest_timing.json, 512 queries: brute 0.053 ms against build + tree 0.103 ms at 64 faces,
+# 0.165 against 0.135 at 256 -- the lines cross near 180 faces; the tree alone wins from 64 faces on (0.041 ms)
+CLOSEST_BRUTE_MAX_FACES = 128
+
+
+def _query_points(points, dev, what):
+    if not torch.is_tensor(points) or points.dim() != 2 or points.shape[1] != 3 or points.dtype != torch.float32:
+        raise ValueError(f"{what}: points must be a (n, 3) fp32 tensor")
+    if points.device != dev:
+        raise ValueError(f"{what}: the points are on {points.device}, the mesh on {dev}")
+    if points.shape[0] > 2 ** 31 - 1:
+        raise ValueError(f"{what}: points must hold at most 2^31 - 1 points")
+    return points.detach().contiguous()
+
+
+def _normals_arg(normals, V, F, dev, what):
+    if normals is None:
+        return None
+    if not isinstance(normals, (tuple, list)) or len(normals) != 2:
+        raise ValueError(f"{what}: normals must be a MeshNormals (pseudonormals(mesh))")
+    for t, shape, name in ((normals[0], (V, 3), "vertex"), (normals[1], (F, 3, 3), "edge")):
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != shape or t.device != dev:
+            raise ValueError(f"{what}: normals.{name} must be a {shape} fp32 tensor on {dev}")
+    return MeshNormals(normals[0].contiguous(), normals[1].contiguous())
+
+
+@torch.no_grad()
+def pseudonormals(mesh) -> MeshNormals:
+    """The tables of the sign test of closest_point: per vertex the sum of angle x unit face normal over the corners there, per
+    (face, edge) the sum of the unit normals of all faces on that edge -- fp64 sums in ascending face order, rounded to fp32 once
+    (include/i2sdf.h, "Closest point").  Corners and half-edges are grouped by two stable torch.sort calls; no floating-point
+    atomics, so the tables are bitwise reproducible.  Accepts a Mesh, a (verts, faces) pair or a MeshBVH.  Enqueues only."""
+    m = _raycast_mesh(mesh, "pseudonormals", cpu_ok=True)
+    verts, faces = m[0], m[1]
+    if not verts.is_cuda:
+        raise L.I2SDFError(f"pseudonormals: the mesh is on {verts.device}; the tables are built on the GPU only, there is no CPU path")
+    lib = L.load()
+    V, F, dev = verts.shape[0], faces.shape[0], verts.device
+    if F > L.BVH_MAX_FACES:
+        raise ValueError(f"pseudonormals: {F} faces are more than the {L.BVH_MAX_FACES} supported")
+    with torch.cuda.device(dev):
+        vn = torch.empty(V, 3, dtype=torch.float32, device=dev)
+        en = torch.empty(F, 3, 3, dtype=torch.float32, device=dev)
+        keys = torch.empty(6 * F, dtype=torch.int64, device=dev)
+        status = torch.empty(1, dtype=torch.int32, device=dev)
+        st = L.stream_ptr()
+        L.check(lib.i2sdf_closest_normal_keys(L.ptr(verts), V, L.ptr(faces), F, L.ptr(keys), L.ptr(status), st), "i2sdf_closest_normal_keys")
+        ck, cp = torch.sort(keys[:3 * F], stable=True)           # stable: a run stays in ascending corner, hence face, order
+        ek, ep = torch.sort(keys[3 * F:], stable=True)
+        skeys, perm = torch.cat([ck, ek]), torch.cat([cp, ep])
+        L.check(lib.i2sdf_closest_normals(L.ptr(verts), V, L.ptr(faces), F, L.ptr(skeys), L.ptr(perm), L.ptr(vn), L.ptr(en), st),
+                "i2sdf_closest_normals")
+    return MeshNormals(vn, en)
+
+
+@torch.no_grad()
+def closest_point(bvh_or_mesh, points, max_dist: float = float("inf"), normals=None, route: str = "auto") -> ClosestPoints:
+    """The point of the mesh closest to every query point within `max_dist`, by the fp64 rule of include/i2sdf.h ("Closest point"):
+    the smallest squared distance, among equal ones the smallest face index -- the same bits by every route.  `feature` says whether
+    it lies inside the face, on one of its edges or at one of its vertices.  With normals=pseudonormals(mesh), `sdist` carries the
+    inside (-) / outside (+) sign of the angle-weighted pseudonormal test; it means something only on a closed, consistently
+    oriented mesh.  A point farther than max_dist from every face (or with a non-finite coordinate) is a miss: face -1, dist +inf.
+    route: "bvh" (a bare mesh gets its tree built first), "brute" (every point against every face: the reference route), "auto" (the
+    tree when one is given or the mesh has more than CLOSEST_BRUTE_MAX_FACES faces).  Enqueues only."""
+    what = "closest_point"
+    if route not in RAYCAST_ROUTES:
+        raise ValueError(f"{what}: route = {route!r} is none of {list(RAYCAST_ROUTES)}")
+    max_dist = float(max_dist)
+    if not max_dist >= 0.0:
+        raise ValueError(f"{what}: max_dist = {max_dist} must be >= 0 (inf allowed)")
+    m = _raycast_mesh(bvh_or_mesh, what, cpu_ok=True)
+    verts, faces = m[0], m[1]
+    dev = verts.device
+    p = _query_points(points, dev, what)
+    n, V, F = p.shape[0], verts.shape[0], faces.shape[0]
+    nm = _normals_arg(normals, V, F, dev, what)
+    if not verts.is_cuda:
+        raise L.I2SDFError(f"{what}: the mesh is on {dev}; closest-point queries run on the GPU only, there is no CPU path")
+    lib = L.load()
+    if route == "auto":
+        route = "bvh" if isinstance(m, MeshBVH) or F > CLOSEST_BRUTE_MAX_FACES else "brute"
+    if route == "bvh" and not isinstance(m, MeshBVH):
+        m = build_bvh(m)
+    with torch.cuda.device(dev):
+        dist = torch.empty(n, dtype=torch.float32, device=dev)
+        point = torch.empty(n, 3, dtype=torch.float32, device=dev)
+        face = torch.empty(n, dtype=torch.int32, device=dev)
+        bary = torch.empty(n, 2, dtype=torch.float32, device=dev)
+        feature = torch.empty(n, dtype=torch.uint8, device=dev)
+        sdist = torch.empty(n, dtype=torch.float32, device=dev) if nm is not None else None
+        status = torch.empty(1, dtype=torch.int32, device=dev)
+        # (an empty tensor has no address: the tables of an empty mesh and the outputs of an empty query are never touched)
+        one = torch.empty(1, dtype=torch.float32, device=dev)
+        tab = (None, None) if nm is None else tuple(L.ptr(t) if t.numel() else L.ptr(one) for t in nm)
+        sd = None if nm is None else (L.ptr(sdist) if n else L.ptr(one))
+        args = (L.ptr(p), n, max_dist, *tab, L.ptr(dist), L.ptr(point), L.ptr(face), L.ptr(bary), L.ptr(feature), sd, L.ptr(status),
+                L.stream_ptr())
+        if route == "bvh":
+            L.check(lib.i2sdf_closest_bvh(L.ptr(m.buffer), L.ptr(verts), V, L.ptr(faces), F, *args), "i2sdf_closest_bvh")
+        else:
+            L.check(lib.i2sdf_closest_brute(L.ptr(verts), V, L.ptr(faces), F, *args), "i2sdf_closest_brute")
+    return ClosestPoints(dist, point, face, bary, feature, sdist, status)
+
+
+def signed_distance(bvh_or_mesh, points, normals=None, max_dist: float = float("inf")) -> torch.Tensor:
+    """(n,) fp32: the distance to the mesh, negative inside -- the quantity the implicit network approximates, at the same points.
+    Builds the pseudonormal tables when they are not given (keep them, and a MeshBVH, when asking more than once).  +inf beyond
+    max_dist.  The sign means something only on a closed, consistently oriented mesh."""
+    if normals is None:
+        normals = pseudonormals(bvh_or_mesh)
+    return closest_point(bvh_or_mesh, points, max_dist, normals).sdist
+
+
+@torch.no_grad()
+def surface_scores(pred, trgt, n_samples: int, threshold: float = 0.05, draws=None, generator=None) -> dict:
+    """The five numbers of `evaluate`, taken from surface to surface instead of from vertex set to vertex set: `n_samples`
+    area-weighted samples of each mesh (sample_surface) against the closest point of the OTHER mesh's surface,
+        'Acc' = mean(d(pred samples -> trgt)), 'Comp' = mean(d(trgt samples -> pred)), 'Prec' = mean(Acc distances < threshold),
+        'Recal' = mean(Comp distances < threshold), 'F-score' = 2 Prec Recal / (Prec + Recal).
+    The means are fp64 sums in a fixed order, as in evaluate.  pred, trgt: a Mesh, a (verts, faces) pair or a MeshBVH (its tree is
+    used).  draws: {"pred": {...}, "trgt": {...}} of sample_surface draws; missing ones come from torch.rand with `generator`.
+    The values are 0-d fp64 device tensors: nothing is read back here (so face indices are not validated: a bad one shows as
+    CLOSEST_BAD_FACE does in closest_point, and its face is never drawn closest).  evaluate is unchanged."""
+    what = "surface_scores"
+    meshes = [_raycast_mesh(pred, what, cpu_ok=True), _raycast_mesh(trgt, what, cpu_ok=True)]      # (both shapes before any device)
+    if meshes[0][0].device != meshes[1][0].device:
+        raise ValueError(f"{what}: pred and trgt must be on the same device")
+    if not meshes[0][0].is_cuda:
+        raise L.I2SDFError(f"{what}: the meshes are on {meshes[0][0].device}; scoring runs on the GPU only, there is no CPU path")
+    n_samples, threshold = int(n_samples), float(threshold)
+    if n_samples <= 0:
+        raise ValueError(f"{what}: n_samples must be positive")
+    if threshold != threshold:
+        raise ValueError(f"{what}: threshold is NaN")
+    for m, name in zip(meshes, ("pred", "trgt")):
+        if m[1].shape[0] == 0:
+            raise ValueError(f"{what}: {name} has no faces")
+    draws = draws or {}
+    trees = [build_bvh(m) for m in meshes]
+    samples = [sample_surface((m[0], m[1]), n_samples, draws.get(name), generator, _check=False)[0]
+               for m, name in zip(meshes, ("pred", "trgt"))]
+    dist2 = closest_point(trees[1], samples[0]).dist          # pred samples -> trgt surface
+    dist1 = closest_point(trees[0], samples[1]).dist          # trgt samples -> pred surface
+    lib = L.load()
+    dev = dist1.device
+    with torch.cuda.device(dev):
+        st = L.stream_ptr()
+        sums = torch.empty(2, 2, dtype=torch.float64, device=dev)                  # rows: dist2 (pred), dist1 (trgt); (sum, count)
+        for row, d in enumerate((dist2, dist1)):
+            ws = torch.empty(int(lib.i2sdf_points_reduce_workspace_bytes(d.shape[0])), dtype=torch.uint8, device=dev)
+            L.check(lib.i2sdf_points_threshold_reduce(L.ptr(d), d.shape[0], threshold, L.ptr(ws), L.ptr(sums[row]), st),
+                    "i2sdf_points_threshold_reduce")
+        m = sums / torch.tensor([[float(n_samples)]], dtype=torch.float64, device=dev)
+        f = 2.0 * m[0, 1] * m[1, 1] / (m[0, 1] + m[1, 1])
+    return {"Acc": m[0, 0], "Comp": m[1, 0], "Prec": m[0, 1], "Recal": m[1, 1], "F-score": f}

@@ -1338,6 +1338,115 @@ int i2sdf_mesh_trace_brute(const float* verts, int64_t V, const int32_t* faces, 
                            const float* t_min, const float* t_max, int64_t n, int32_t cull, int32_t any_hit, float* t, int32_t* face,
                            float* bary, uint8_t* hit, int32_t* status, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Closest point -- the point of a triangle mesh nearest to a query point, its distance, and the inside / outside sign: what trimesh's
+ * `proximity` and open3d's compute_closest_points / compute_signed_distance answer on the host.  The reference has no such query of
+ * its own (it calls those libraries), so the rule is defined here.  csrc/closest.hip, csrc/tri_closest.h; the tree is the one of "Ray
+ * casting" above, unchanged.  No plan.  Every call only enqueues on `stream`: no allocation, no synchronisation, no host read.
+ * tests/closest_ref.py restates the rule and the tables in numpy.
+ *
+ * The law.  verts (V, 3) fp32, faces (F, 3) int32, points (n, 3) fp32, one max_dist (fp32, >= 0 or +inf).
+ *   Arithmetic.  fp64 on the exact images of the fp32 inputs; every operation is ONE IEEE operation, rounded to nearest, in the order
+ *         written, none contracted into an FMA; a dot product x.y is (x0 y0 + x1 y1) + x2 y2.  fp64 and not the ray law's fp32: a closest
+ *         point computed in fp32 is off by ulps of the COORDINATE (2.4e-7 at a coordinate of 2), so that a distance of 1e-4 to the
+ *         surface -- the interesting range when an SDF is compared with a mesh -- would carry a relative error of 1e-3.
+ *   Face (A, B, C) and point p (Ericson, Real-Time Collision Detection, 5.1.5); the first region that applies decides:
+ *         ab = B - A, ac = C - A, ap = p - A, d1 = ab.ap, d2 = ac.ap.      d1 <= 0 and d2 <= 0: VERT_A, c = A.
+ *         bp = p - B, d3 = ab.bp, d4 = ac.bp.                              d3 >= 0 and d4 <= d3: VERT_B, c = B.
+ *         vc = d1 d4 - d3 d2.     vc <= 0 and d1 >= 0 and d3 <= 0: EDGE_AB, v = d1 / (d1 - d3), c = A + v ab.
+ *         cp = p - C, d5 = ab.cp, d6 = ac.cp.                              d6 >= 0 and d5 <= d6: VERT_C, c = C.
+ *         vb = d5 d2 - d1 d6.     vb <= 0 and d2 >= 0 and d6 <= 0: EDGE_CA, w = d2 / (d2 - d6), c = A + w ac.
+ *         va = d3 d6 - d5 d4.     va <= 0 and d4 - d3 >= 0 and d5 - d6 >= 0: EDGE_BC, w = (d4 - d3) / ((d4 - d3) + (d5 - d6)),
+ *                                 c = B + w (C - B).
+ *         Otherwise FACE: den = 1 / ((va + vb) + vc), v = vb den, w = vc den, c = (A + v ab) + w ac.
+ *         d^2 = (p - c).(p - c).  The weights (of A, of B), in fp64: VERT_A (1, 0), VERT_B (0, 1), VERT_C (0, 0), EDGE_AB (1 - v, v),
+ *         EDGE_CA (1 - w, 0), EDGE_BC (0, 1 - w), FACE ((1 - v) - w, v).
+ *   Faces that are never closest: those the ray law never hits for their indices or vertices (an index outside [0, V), a non-finite
+ *         vertex: they set I2SDF_CLOSEST_BAD_FACE in every query of that mesh, whatever the points), and faces whose ab x ac --
+ *         (ab1 ac2 - ab2 ac1, ab2 ac0 - ab0 ac2, ab0 ac1 - ab1 ac0) -- is exactly zero in all three components: the zero-area faces
+ *         marching cubes emits.
+ *   Result per point: among the faces with d^2 <= (double)max_dist * (double)max_dist (a NaN d^2 fails that) the smallest d^2; among
+ *         equal d^2 the smallest face index.  An order-free function of the inputs, so bitwise reproducible and the same by every
+ *         route.  dist = (float)sqrt(d^2), point = (float)c, face, bary = the two weights rounded to fp32 (as in the ray caster's
+ *         results), feature = one of I2SDF_CLOSEST_*.  No face counts (F = 0 too): face = -1, dist = +inf, point = bary = feature = 0.
+ *         A point with a non-finite coordinate is such a miss and sets I2SDF_CLOSEST_BAD_POINT.
+ *   *status: the OR of the two bits over the call.
+ *   Sign (when the tables below are given): s = ((p - c).N >= 0) ? +1 : -1, sdist = s * dist (+inf on a miss), with c the unrounded
+ *         fp64 closest point and N the entry of the closest feature, widened to fp64: the edge entry enormal[face][edge] for an edge,
+ *         vnormal[vertex] for a vertex, and for FACE the face's own ab x ac as above (not normalised: only its direction matters).
+ *         This is the angle-weighted pseudonormal test of Baerentzen and Aanaes (Signed distance computation using the angle weighted
+ *         pseudonormal, IEEE TVCG 2005).  On a closed, consistently oriented mesh (right-hand normals outward) it is the inside (-) /
+ *         outside (+) sign.  ON ANYTHING ELSE -- an open sheet, a soup, mixed orientations, self-intersections -- IT IS DEFINED AS
+ *         ABOVE BUT MEANS NOTHING.
+ *
+ * The tables: vnormal (V, 3) fp32, enormal (F, 3, 3) fp32 indexed [face][AB, BC, CA].  Over the faces that may be closest, in fp64:
+ *         n_f = (ab x ac) / sqrt((ab x ac).(ab x ac)), each component divided.  vnormal[i] = the sum, in ascending face index, of
+ *         angle * n_f over the corners at vertex i, angle = atan2(sqrt(x.x), e1.e2), x = e1 x e2, e1 and e2 the edges from the corner to
+ *         the next and to the previous vertex of the face.  enormal[f][e] = the sum, in ascending face index, of n_f over ALL faces
+ *         that contain that undirected edge (two on a manifold, one on a boundary).  Each sum starts from 0, adds `angle * n_f`
+ *         (one product, one sum per component) and is rounded to fp32 once.  Vertices and faces outside those faces get 0.
+ *         (atan2 is not correctly rounded, so the tables are reproducible on one build and within an fp32 ulp across libraries.)
+ *   Grouping works as the tree's keys do: i2sdf_closest_normal_keys writes 3 F corner keys (the vertex index) followed by 3 F
+ *         half-edge keys (min << 32 | max), entry 3 f + k for corner / edge k of face f, INT64_MAX for faces that are never closest;
+ *         the CALLER sorts EACH half on its own, stably, ascending, with its permutation (torch.sort(stable=True): positions 0 .. 3F-1
+ *         inside the half); i2sdf_closest_normals takes both halves back, concatenated, and reduces every run in order.  No
+ *         floating-point atomics: the tables are bitwise reproducible from run to run.  One lane walks one run, so a vertex shared by
+ *         very many faces (a fan of 10^5) serialises; meshes from marching cubes have valence about 6.
+ *
+ * Two routes with the same bits.
+ * i2sdf_closest_bvh: one lane per query through the tree.  The child with the smaller box distance first, the other on the per-lane
+ *   stack of 64 slots in LDS (as the trace).  64 suffice for every tree i2sdf_bvh_build makes: a key has 63 significant bits (a 31-bit
+ *   code, a 32-bit face index) and every level of Karras' tree splits at a further bit of the keys, so no leaf is deeper than 63; the
+ *   walk is depth-first and holds at most one pending sibling per level of its current path, hence at most 63 entries.  (A buffer that
+ *   is not such a tree cannot overrun the stack or loop -- pushes beyond 64 are dropped, visits are capped at 2 F -- but its result
+ *   means nothing, as with the trace.)  A pending child is NOT tested again when it is popped (its box distance is not kept): it is
+ *   fetched and its own children are tested against the bound of that moment.  q = (e0^2 + e1^2) + e2^2, e_k = max(lo_k - p_k, p_k - hi_k, 0), in fp64.  A child is
+ *   skipped iff  q > (sqrt(b) (1 + 2^-20) + 2^-32 M)^2,  b = the best d^2 so far (max_dist^2 before there is one), M = the largest
+ *   coordinate magnitude of p and of the mesh's bounds (the tree's header).  q equal to b is ENTERED, since a tie may go to a smaller
+ *   face index; a NaN on either side never skips; b = +inf skips nothing.  This is conservative with respect to the RULE, not to the
+ *   geometry -- the computed c can lie outside the box by rounding, so a computed d^2 can be below the true box distance:
+ *   (edges, vertices)  Rounding is monotone, so the computed parameter of an edge case lies in [0, 1] exactly (d1 >= 0 >= d3 gives
+ *         0 <= d1 <= d1 - d3, and so on), and each component of c = A + v ab lies between the computed A + 0 and A + ab, which is B up to
+ *         2 u |B - A|, u = 2^-53.  With the roundings of p - c and of the sum of squares: sqrt(d^2) >= sqrt(q) (1 - 4 u) - 8 u M.
+ *   (FACE)  With e = the error of the computed v and w, c lies within e (|ab| + |ac|) + 8 u M of the triangle.  va, vb, vc are
+ *         differences of products of dot products, each good to 8 u |ab| |ac| |ap|^2-ish absolutely, and their sum is |ab x ac|^2, so
+ *         e <= 2^-49 |ab| |ac| |p - A|^2 / |ab x ac|^2.  A relative term alone cannot cover this: d can be 0 while the coordinates are
+ *         1000, and e (|ab| + |ac|) is then an absolute error in units of the coordinates.  The slack sqrt(b) 2^-20 + 2^-32 M covers
+ *         every face with  L^3 |p - A| <= 2^28 |ab x ac|^2 (far queries, sqrt(b) ~ |p - A|, L the longest edge)  and
+ *         L^5 <= 2^16 M |ab x ac|^2 (near queries, |p - A| <= L): a face of extent 2^-7 M may be a sliver of aspect 2^-11.  THE
+ *         DERIVATION ASSUMES THAT; for thinner slivers the FACE branch of the rule is itself ill-conditioned and the two routes may
+ *         differ there.  (It also assumes that no product underflows; coordinates of ordinary magnitude do not.)
+ *   The threshold is rounded like any other fp64 expression; the factor 2 between the bounds above and the constants absorbs that.
+ * i2sdf_closest_brute: every query against every face through the same inline function: the reference route and the small-mesh route.
+ *
+ *   points (n, 3); dist (n) fp32, point (n, 3) fp32, face (n) int32, bary (n, 2) fp32, feature (n) uint8, status (1) int32.
+ *   vnormal, enormal, sdist (n) fp32: all three or all NULL.  0 <= n < 2^31; n = 0 still reports the face bit.  i2sdf_closest_bvh takes
+ *   the SAME verts, faces, F the tree was built from (the sign reads them; the search reads only the tree).
+ *   keys (6 F) int64; sorted_keys, perm (6 F) int64: the two sorted halves, concatenated.
+ * Refused with I2SDF_EINVAL before any launch: a NULL or misaligned pointer (stream excepted; mesh pointers when F = 0, query
+ *   pointers when n = 0 and vnormal when V = 0 too), F outside 0..I2SDF_BVH_MAX_FACES, V outside 0..2^31-1, n outside the range, a
+ *   negative or NaN max_dist, only some of vnormal / enormal / sdist.
+ * ---------------------------------------------------------------------------------------------- */
+#define I2SDF_CLOSEST_BAD_POINT 1     /* status bit 0 */
+#define I2SDF_CLOSEST_BAD_FACE 2      /* status bit 1 */
+#define I2SDF_CLOSEST_FACE 0
+#define I2SDF_CLOSEST_EDGE_AB 1
+#define I2SDF_CLOSEST_EDGE_BC 2
+#define I2SDF_CLOSEST_EDGE_CA 3
+#define I2SDF_CLOSEST_VERT_A 4
+#define I2SDF_CLOSEST_VERT_B 5
+#define I2SDF_CLOSEST_VERT_C 6
+int i2sdf_closest_bvh(const void* bvh, const float* verts, int64_t V, const int32_t* faces, int64_t F, const float* points, int64_t n,
+                      float max_dist, const float* vnormal, const float* enormal, float* dist, float* point, int32_t* face, float* bary,
+                      uint8_t* feature, float* sdist, int32_t* status, void* stream);
+int i2sdf_closest_brute(const float* verts, int64_t V, const int32_t* faces, int64_t F, const float* points, int64_t n, float max_dist,
+                        const float* vnormal, const float* enormal, float* dist, float* point, int32_t* face, float* bary,
+                        uint8_t* feature, float* sdist, int32_t* status, void* stream);
+int i2sdf_closest_normal_keys(const float* verts, int64_t V, const int32_t* faces, int64_t F, int64_t* keys, int32_t* status,
+                              void* stream);
+int i2sdf_closest_normals(const float* verts, int64_t V, const int32_t* faces, int64_t F, const int64_t* sorted_keys, const int64_t* perm,
+                          float* vnormal, float* enormal, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
