@@ -98,6 +98,7 @@ BVH_MAX_FACES = 1 << 28          # I2SDF_BVH_MAX_FACES
 CLOSEST_BAD_POINT, CLOSEST_BAD_FACE = 1, 2  # I2SDF_CLOSEST_*: status bits
 # I2SDF_CLOSEST_FACE ... I2SDF_CLOSEST_VERT_C: the feature of the face the closest point lies on
 CLOSEST_FEATURES = {"FACE": 0, "EDGE_AB": 1, "EDGE_BC": 2, "EDGE_CA": 3, "VERT_A": 4, "VERT_B": 5, "VERT_C": 6}
+WINDING_BAD_POINT, WINDING_BAD_FACE = 1, 2  # I2SDF_WINDING_*: status bits
 TRACE_HIT, TRACE_MISS, TRACE_UNRESOLVED, TRACE_INSIDE = 1, 2, 3, 4      # I2SDF_TRACE_*: status of a traced ray
 TRACE_ROUTES = {"auto": 0, "stepwise": 1, "fused": 2}                   # I2SDF_TRACE_AUTO / _STEPWISE / _FUSED
 TRACE_MAX_STEPS = 1024           # I2SDF_TRACE_MAX_STEPS
@@ -294,6 +295,13 @@ SIGNATURES = {
     "i2sdf_closest_normal_keys": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _P]),
     # verts, V, faces, F, sorted_keys, perm, vnormal, enormal, stream
     "i2sdf_closest_normals": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _P, _P, _P]),
+    "i2sdf_winding_moments_bytes": (_I64, [_I64]),
+    # bvh, F, moments, stream
+    "i2sdf_winding_moments": (C.c_int, [_P, _I64, _P, _P]),
+    # bvh, moments, F, points, n, beta, w_out, status, stream
+    "i2sdf_winding_bvh": (C.c_int, [_P, _P, _I64, _P, _I64, C.c_float, _P, _P, _P]),
+    # verts, V, faces, F, points, n, w_out, status, stream
+    "i2sdf_winding_brute": (C.c_int, [_P, _I64, _P, _I64, _P, _I64, _P, _P, _P]),
     "i2sdf_light_forward": (C.c_int, [_P, _P, _P, _I64, _I64, _P, _P, _P]),
     "i2sdf_light_backward": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _P, _P, _P]),
     "i2sdf_loss_scratch_floats": (_I64, []),

@@ -1447,6 +1447,85 @@ int i2sdf_closest_normal_keys(const float* verts, int64_t V, const int32_t* face
 int i2sdf_closest_normals(const float* verts, int64_t V, const int32_t* faces, int64_t F, const int64_t* sorted_keys, const int64_t* perm,
                           float* vnormal, float* enormal, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Winding number -- the generalized winding number of a triangle mesh at a query point (Jacobson, Kavan, Sorkine-Hornung: Robust
+ * inside-outside segmentation using generalized winding numbers, SIGGRAPH 2013): 1 inside a closed, outward-oriented mesh, 0 outside,
+ * and a smooth function in between on the meshes "Closest point" gives no sign for -- open sheets, culled or cut level sets, rooms
+ * seen from inside, soups.  |w| > 0.5 is the inside test.  csrc/winding.hip, csrc/tri_solid_angle.h; the tree is the one of "Ray
+ * casting" above, unchanged and only read.  No plan.  Every call only enqueues on `stream`: no allocation, no synchronisation, no
+ * host read.  tests/winding_ref.py restates the term, the moments and the rule in numpy.
+ *
+ * The law.  verts (V, 3) fp32, faces (F, 3) int32, points (n, 3) fp32.   w(q) = (1 / 4 pi) sum_f Omega_f(q).
+ *   Arithmetic.  fp64 on the exact images of the fp32 inputs; every operation is ONE IEEE operation, rounded to nearest, in the order
+ *         written, none contracted into an FMA; a dot product x.y is (x0 y0 + x1 y1) + x2 y2.
+ *   Face (A, B, C) and point q (Van Oosterom and Strackee, The solid angle of a plane triangle, IEEE Trans. Biomed. Eng. 1983):
+ *         a = A - q, b = B - q, c = C - q;  la = sqrt(a.a), lb = sqrt(b.b), lc = sqrt(c.c);  x = b x c =
+ *         (b1 c2 - b2 c1, b2 c0 - b0 c2, b0 c1 - b1 c0);  det = a.x;  den = (((la lb) lc + (a.b) lc) + (b.c) la) + (c.a) lb;
+ *         Omega = 2 atan2(det, den).  Positive when the right-hand normal (B - A) x (C - A) points away from q.
+ *         atan2 is the library's: it is not correctly rounded, so w is reproducible on one build and within the library's bound
+ *         times the number of faces summed across builds; det and den are the same bits everywhere.
+ *   Faces that contribute 0: those the ray law never hits for their indices or vertices (an index outside [0, V), a non-finite
+ *         vertex: they set I2SDF_WINDING_BAD_FACE in every query of that mesh, whatever the points).  Zero-area faces are NOT taken
+ *         out: their det is 0 up to rounding and the formula gives 0 (or +-2 pi on the degenerate segment itself).
+ *   A point with a non-finite coordinate gives NaN and sets I2SDF_WINDING_BAD_POINT.  A point ON the surface gets what the formula
+ *         gives -- atan2(0, 0) = 0 at a vertex and where den cancels inside an edge, atan2(+-0, < 0) = +-pi inside a face -- always
+ *         finite.  F = 0: w = 0.
+ *   w = sum / (4 pi), 4 pi = 4 * M_PI as an fp64 constant, one division.  *status: the OR of the two bits over the call.
+ *
+ * The far field (Barill, Dickson, Schmidt, Levin, Jacobson: Fast winding numbers for soups and clouds, SIGGRAPH 2018; orders 0, 1).
+ *   Per internal node of the tree, over the faces below it (a_f n_f = 1/2 (B - A) x (C - A) the area vector, each component one
+ *   difference of products times 0.5; a_f = sqrt of its dot with itself; c_f = ((A + B) + C) / 3 the face centroid):
+ *         p~ = (sum a_f c_f) / (sum a_f)        the area-weighted centroid;
+ *         N0 = sum a_f n_f;     N1 = sum (c_f - p~) (x) (a_f n_f), N1_ij = (c_f - p~)_i (a_f n_f)_j -- exact for triangles;
+ *         r  = the largest distance from p~ to a corner of the node's box (the union of the two child boxes the tree stores):
+ *              e_k = max(p~_k - lo_k, hi_k - p~_k), r = sqrt(e.e).  Conservative: every face below lies inside the box.
+ *   With rho = p~ - q, d2 = rho.rho: iff  d2 > beta^2 r^2  (fp64; beta^2 = (double)beta (double)beta, r^2 = r r, one product each; a
+ *   NaN on either side is "no") the node contributes
+ *         Omega ~ rho.N0 / d^3 + ((N1_00 + N1_11) + N1_22) / d^3 - 3 (sum_ij (rho_i rho_j) N1_ji) / d^5,
+ *         d = sqrt(d2), d^3 = d2 d, d^5 = d^3 d2, the double sum i-major from 0, and nothing below it is visited; otherwise both
+ *   children are visited, child 0 first.  A leaf contributes the exact term.  The sum is fp64 in visit order, so the result is a
+ *   fixed function of (tree, table, q, beta) -- bitwise reproducible -- but NOT the same bits as the brute route.
+ *   beta = +inf accepts no node (inf * 0 is NaN, also "no"): the exact sum in tree order.  beta = 2 is the default of the paper.
+ *   What the approximation costs is measured in tests/test_winding_ref.py, against the exact sum, at queries at least 0.05 of the
+ *   diameter from the surface (icosphere of 1280 faces, an open cap of it, a 3000-face soup; the Karras tree, box radii):
+ *           icosphere(3), 1280 faces   beta = 2: 5.11e-2 (39 terms per query)    beta = 3: 2.15e-2 (97 terms per query)
+ *           open cap of it, 456 faces  beta = 2: 2.17e-2 (28)                    beta = 3: 7.65e-3 (65)
+ *           soup, 3000 faces           beta = 2: 3.11e-3 (50)                    beta = 3: 1.04e-3 (178)
+ *         (500 queries each.  On meshes this small the order-1 term does not lower the maximum; it does lower the far field of a
+ *         single node as the law says, d^-4 against d^-3: the same test file holds that.)
+ *   No bar is set for these; the properties held are that round(w) is round(w_exact) at every such query at beta = 2 and that the
+ *   largest error at beta = 3 is below that at beta = 2.
+ *
+ * The moments are composable, so one bottom-up pass over the tree's parent links fits them (i2sdf_winding_moments): per node
+ *         A = sum a_f,  S = sum a_f c_f,  N0,  M = sum (c_f - o) (x) (a_f n_f),   o = ((lo + hi) 0.5) of the root box (the header),
+ *   so that a mesh shifted by +1000 does not cancel; a parent is child 0 + child 1 in that order whatever the arrival order, so the
+ *   table is bitwise reproducible; then p~ = S / A, N1_ij = M_ij - (p~_i - o_i) N0_j.  A = 0 (nothing but degenerate or rejected faces
+ *   below) gives r = +inf: such a node is always descended.
+ *   The table: 16 fp64 per internal node i at moments + 128 i: p~[3], r, N0[3], N1[9] (row-major).  i2sdf_winding_moments_bytes(F) =
+ *   128 max(F - 1, 0) + the build's own arrival counters (4 bytes per node, rounded up to 16) + 16: never 0 for a legal F, 0 for
+ *   F < 0 or F > I2SDF_BVH_MAX_FACES.  The tree buffer and i2sdf_bvh_bytes are unchanged; the tree is not written (the counters
+ *   of its own build are left alone, so a tree may be shared between streams).
+ *
+ * i2sdf_winding_bvh: one lane per query, child 0 first, child 1 on the per-lane stack of 64 slots in LDS (as the trace; the tree is at
+ *   most 63 deep, pushes beyond 64 are dropped and visits capped at 2 F for a buffer that is not such a tree).
+ * i2sdf_winding_brute: every query against every face in ascending face order through the same inline function: the reference route
+ *   and the small-mesh route.
+ *
+ *   points (n, 3) fp32; w_out (n) fp64; status (1) int32.  0 <= n < 2^31; n = 0 still reports the face bit.  bvh: the buffer
+ *   i2sdf_bvh_build filled for the same F; moments: i2sdf_winding_moments_bytes(F) bytes, 16-byte aligned, filled by
+ *   i2sdf_winding_moments from that tree.  F = 0, 1 (no node: the table is empty) and 2 are legal.
+ * Refused with I2SDF_EINVAL before any launch: a NULL or misaligned pointer (stream excepted; mesh pointers when F = 0 and query
+ *   pointers when n = 0 too), F outside 0..I2SDF_BVH_MAX_FACES, V outside 0..2^31-1, n outside the range, a negative or NaN beta.
+ * ---------------------------------------------------------------------------------------------- */
+#define I2SDF_WINDING_BAD_POINT 1     /* status bit 0 */
+#define I2SDF_WINDING_BAD_FACE 2      /* status bit 1 */
+int64_t i2sdf_winding_moments_bytes(int64_t F);
+int i2sdf_winding_moments(const void* bvh, int64_t F, void* moments, void* stream);
+int i2sdf_winding_bvh(const void* bvh, const void* moments, int64_t F, const float* points, int64_t n, float beta, double* w_out,
+                      int32_t* status, void* stream);
+int i2sdf_winding_brute(const float* verts, int64_t V, const int32_t* faces, int64_t F, const float* points, int64_t n, double* w_out,
+                        int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
