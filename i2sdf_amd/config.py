@@ -20,6 +20,15 @@ def _has(node, key):
     return hasattr(node, key)
 
 
+MAX_HIDDEN_LAYERS = 11      # include/i2sdf.h: I2SDF_MAX_LAYERS (12) linear layers per net, the output layer among them
+
+
+def _check_depth(key, dims):
+    if not 1 <= len(dims) <= MAX_HIDDEN_LAYERS:
+        raise NotImplementedError(f"{key} has {len(dims)} hidden layers: the plan's descriptor and the kernels' layer loops hold 1..{MAX_HIDDEN_LAYERS} "
+                                  f"hidden layers per net (include/i2sdf.h: I2SDF_MAX_LAYERS = {MAX_HIDDEN_LAYERS + 1} linear layers)")
+
+
 @dataclass
 class MlpShape:
     """One weight-normed nn.Linear stack."""
@@ -124,6 +133,13 @@ class NetConfig:
         skip_in = tuple(_get(inet, "skip_in", ()))
         if len(skip_in) > 1:
             raise NotImplementedError("at most one skip connection")
+        _check_depth("implicit_network.dims", hid)
+        _check_depth("rendering_network.dims", list(_get(rnet, "dims")))
+        if skip_in and not 1 <= int(skip_in[0]) < len(hid):
+            raise NotImplementedError(
+                f"implicit_network.skip_in {list(skip_in)} with {len(hid)} hidden layers: the SDF kernels concatenate PE(x) in front of a hidden "
+                f"layer behind the first one -- {f'entries 1..{len(hid) - 1}' if len(hid) > 1 else 'no entry'} here (layer 0 reads PE(x) "
+                f"already; entry {len(hid)} would be the output layer, which the kernels evaluate as row vectors over the hidden width)")
         pe = d_in + 2 * d_in * multires
         full = [pe] + hid + [d_out + fvs]
         dims = []
@@ -188,6 +204,11 @@ class NetConfig:
         light = None
         if _has(conf, "light_network"):
             lhid = list(_get(_get(conf, "light_network"), "dims"))
+            if lhid not in ([128], [32]) or (fvs, lhid[0]) not in ((256, 128), (64, 32)):
+                raise NotImplementedError(
+                    f"light_network.dims {lhid} at feature_vector_size {fvs}: the light head's kernels are instantiated for one hidden layer of 128 "
+                    "at feature size 256 (synthetic_light_mask.yml) and of 32 at feature size 64 (plumbing size) only; add an instantiation in "
+                    "csrc/mlp_train.hip (light_fwd_kernel, light_bwd_kernel) for another head")
             lfull = [fvs] + lhid + [1]
             light = MlpShape("light_network", [(lfull[l + 1], lfull[l]) for l in range(len(lfull) - 1)], lhid[0], fvs, 0)
         rs = _get(conf, "ray_sampler")

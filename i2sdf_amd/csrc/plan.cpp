@@ -374,6 +374,26 @@ extern "C" int i2sdf_plan_create(const i2sdf_net_desc* desc, i2sdf_plan** out) {
       g_hip_err = "i2sdf_plan_create: the radiance net's 'idr' mode needs d_in 9 (points, view directions, normals)";
       return I2SDF_EINVAL;
     }
+    for (const i2sdf_mlp_desc* d : {&desc->sdf, &desc->rgb})
+      if (d->n_lin < 2 || d->n_lin > I2SDF_MAX_LAYERS) {
+        g_hip_err = std::string("i2sdf_plan_create: ") + (d == &desc->sdf ? "sdf" : "rgb") + ".n_lin " + std::to_string(d->n_lin) +
+                    ": a net has 2.." + std::to_string(I2SDF_MAX_LAYERS) + " linear layers (I2SDF_MAX_LAYERS; 1.." +
+                    std::to_string(I2SDF_MAX_LAYERS - 1) + " hidden layers and the output layer)";
+        return I2SDF_EINVAL;
+      }
+    if (desc->sdf.skip_layer == 0 || desc->sdf.skip_layer >= desc->sdf.n_lin - 1) {
+      g_hip_err = "i2sdf_plan_create: sdf.skip_layer " + std::to_string(desc->sdf.skip_layer) + " with n_lin " + std::to_string(desc->sdf.n_lin) +
+                  ": the SDF kernels concatenate PE(x) in front of a hidden layer behind the first one, layers 1.." +
+                  std::to_string(desc->sdf.n_lin - 2) + " here (-1: no skip); layer 0 reads PE(x) already and the output layer is evaluated as row vectors";
+      return I2SDF_EINVAL;
+    }
+    const i2sdf_mlp_desc& dl = desc->light;
+    if (dl.n_lin != 0 && !(dl.n_lin == 2 && ((dl.hidden == 128 && F == 256) || (dl.hidden == 32 && F == 64)))) {
+      g_hip_err = "i2sdf_plan_create: light.n_lin " + std::to_string(dl.n_lin) + " / light.hidden " + std::to_string(dl.hidden) + " at feature size " +
+                  std::to_string(F) + ": the light head's kernels are instantiated for one hidden layer of 128 at feature size 256 and of 32 at "
+                  "feature size 64 only";
+      return I2SDF_EINVAL;
+    }
   }
   i2sdf_plan* p = new i2sdf_plan();
   p->desc = *desc;
@@ -383,10 +403,16 @@ extern "C" int i2sdf_plan_create(const i2sdf_net_desc* desc, i2sdf_plan** out) {
   if (desc->light.n_lin) assign_scales_and_wgrad(p, p->light, 2);
   p->scale_floats = round_up(p->n_scale, CHUNK_FLOATS);
   Builder b{p->segs, 0};
+  const char* net = "SDF net";
   int rc = build_sdf(p, b);
-  if (!rc) rc = build_rgb(p, b);
-  if (!rc) rc = build_light(p, b);
-  if (rc) { delete p; return rc; }
+  if (!rc) { net = "radiance net"; rc = build_rgb(p, b); }
+  if (!rc) { net = "light head"; rc = build_light(p, b); }
+  if (rc) {
+    g_hip_err = std::string("i2sdf_plan_create: the descriptor of the ") + net + " is inconsistent: its layers' out_dim / in_dim, in0, d_in, d_out or "
+                "multires do not follow from n_lin, hidden, skip_layer and the feature size";
+    delete p;
+    return rc;
+  }
   { Seg z{}; z.type = SEG_ZERO; z.nchunks = SC > SCH ? SC : SCH; b.add(z); }   // slack: the DMA look-ahead may touch one stage past the end
   p->total_chunks = b.chunk;
   p->n_segs = (int32_t)p->segs.size();

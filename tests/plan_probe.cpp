@@ -21,7 +21,10 @@ int main(int argc, char** argv) {
   if (!f || fread(&desc, sizeof(desc), 1, f) != 1) return 2;
   fclose(f);
   i2sdf_plan* p = nullptr;
-  if (i2sdf_plan_create(&desc, &p) != I2SDF_OK) return 3;
+  if (i2sdf_plan_create(&desc, &p) != I2SDF_OK) {
+    fprintf(stderr, "i2sdf_plan_create refused: %s\n", i2sdf_last_hip_error());      // (tests/test_shape_frontier.py reads the reason)
+    return 3;
+  }
   printf("segs %d total_chunks %lld scale_floats %lld\n", p->n_segs, (long long)p->total_chunks, (long long)p->scale_floats);
   for (const Seg& s : p->segs) {
     uint32_t mb;
