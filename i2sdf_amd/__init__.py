@@ -27,7 +27,8 @@ def __getattr__(name):
                 "voxel_down_sample", "nearest_neighbors", "evaluate", "mesh_depth", "tsdf_fuse", "tsdf_integrate", "tsdf_extract",
                 "TsdfVolume", "refuse", "score", "MeshBVH", "RayHits", "build_bvh", "ray_mesh_intersect", "occluded", "ClosestPoints",
                 "MeshNormals", "closest_point", "pseudonormals", "signed_distance", "surface_scores", "WindingMoments", "winding_moments",
-                "winding_number", "inside"):
+                "winding_number", "inside", "simplify_vertex_clustering", "clean", "topology", "SimplifyResult", "CleanResult",
+                "MeshTopology"):
         from . import mesh
         return getattr(mesh, name)
     if name in ("psnr", "ssim", "image_stats", "image_metrics", "to_frames", "interpolate_poses", "pixel_grid", "linear_to_srgb"):

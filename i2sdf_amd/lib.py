@@ -99,6 +99,12 @@ CLOSEST_BAD_POINT, CLOSEST_BAD_FACE = 1, 2  # I2SDF_CLOSEST_*: status bits
 # I2SDF_CLOSEST_FACE ... I2SDF_CLOSEST_VERT_C: the feature of the face the closest point lies on
 CLOSEST_FEATURES = {"FACE": 0, "EDGE_AB": 1, "EDGE_BC": 2, "EDGE_CA": 3, "VERT_A": 4, "VERT_B": 5, "VERT_C": 6}
 WINDING_BAD_POINT, WINDING_BAD_FACE = 1, 2  # I2SDF_WINDING_*: status bits
+SIMPLIFY_CONTRACTIONS = {"quadric": 0, "average": 1}      # I2SDF_SIMPLIFY_QUADRIC / _AVERAGE
+SIMPLIFY_BAD_FACE = 1            # I2SDF_SIMPLIFY_BAD_FACE: status bit
+SIMPLIFY_DROP_REPEATED, SIMPLIFY_DROP_ZERO_AREA = 1, 2    # I2SDF_SIMPLIFY_DROP_*: flags of i2sdf_simplify_face_keys
+# I2SDF_TOPO_*: indices into the counts of i2sdf_mesh_edge_stats
+TOPO = {"EDGES": 0, "BOUNDARY": 1, "MANIFOLD": 2, "NONMANIFOLD": 3, "MISORIENTED": 4, "REPEATED_FACES": 5, "VERTICES": 6, "EULER": 7, "FACES": 8}
+TOPO_COUNTS = 10                 # I2SDF_TOPO_COUNTS
 TRACE_HIT, TRACE_MISS, TRACE_UNRESOLVED, TRACE_INSIDE = 1, 2, 3, 4      # I2SDF_TRACE_*: status of a traced ray
 TRACE_ROUTES = {"auto": 0, "stepwise": 1, "fused": 2}                   # I2SDF_TRACE_AUTO / _STEPWISE / _FUSED
 TRACE_MAX_STEPS = 1024           # I2SDF_TRACE_MAX_STEPS
@@ -302,6 +308,25 @@ SIGNATURES = {
     "i2sdf_winding_bvh": (C.c_int, [_P, _P, _I64, _P, _I64, C.c_float, _P, _P, _P]),
     # verts, V, faces, F, points, n, w_out, status, stream
     "i2sdf_winding_brute": (C.c_int, [_P, _I64, _P, _I64, _P, _I64, _P, _P, _P]),
+    # sorted_keys, perm, head_scan, V, n_cells, vertex_cell, cell_start, stream
+    "i2sdf_simplify_vertex_cells": (C.c_int, [_P, _P, _P, _I64, _I64, _P, _P, _P]),
+    # faces, F, V, vertex_cell, n_cells, corner_keys, status, stream
+    "i2sdf_simplify_corner_keys": (C.c_int, [_P, _I64, _I64, _P, _I64, _P, _P, _P]),
+    # sorted_corner_keys, F, n_cells, corner_runs, stream
+    "i2sdf_simplify_corner_runs": (C.c_int, [_P, _I64, _I64, _P, _P]),
+    # verts, normals, V, faces, F, bounds, voxel_size, reg, contraction, sorted_keys, perm, cell_start, corner_perm, corner_runs, n_cells,
+    # out_verts, out_normals, fallback, stream
+    "i2sdf_simplify_cells": (C.c_int, [_P, _P, _I64, _P, _I64, _P, C.c_double, C.c_double, _I32] + [_P] * 5 + [_I64] + [_P] * 4),
+    # verts, V, faces, F, vertex_map, n_map, flags, out_faces, key_hi, key_lo, status, stream
+    "i2sdf_simplify_face_keys": (C.c_int, [_P, _I64, _P, _I64, _P, _I64, _I32] + [_P] * 5),
+    # sorted_hi, sorted_lo, perm, n, keep, first, stream
+    "i2sdf_simplify_run_heads": (C.c_int, [_P, _P, _P, _I64, _P, _P, _P]),
+    # verts, V, key_hi, key_lo, stream
+    "i2sdf_simplify_position_keys": (C.c_int, [_P, _I64, _P, _P, _P]),
+    # faces, F, V, keys, vflag, counts, status, stream
+    "i2sdf_mesh_edge_stats_keys": (C.c_int, [_P, _I64, _I64, _P, _P, _P, _P, _P]),
+    # sorted_keys, F, counts, stream
+    "i2sdf_mesh_edge_stats": (C.c_int, [_P, _I64, _P, _P]),
     "i2sdf_light_forward": (C.c_int, [_P, _P, _P, _I64, _I64, _P, _P, _P]),
     "i2sdf_light_backward": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _P, _P, _P]),
     "i2sdf_loss_scratch_floats": (_I64, []),

@@ -63,6 +63,13 @@ Inside / outside for meshes that are open, cut or seen from one side (csrc/windi
   * winding_moments     the far-field table of a tree, fitted bottom-up in a fixed order;
   * inside              |winding_number| > 0.5; signed_distance(sign="winding") takes its sign from it.
 Each route bitwise reproducible; tests/winding_ref.py restates the law in numpy.
+
+Between the producers and the consumers (csrc/simplify.hip, csrc/quadric.h; include/i2sdf.h, "Mesh simplification"):
+  * simplify_vertex_clustering  vertex clustering on voxel_down_sample's grid with quadric placement (Lindstrom 2000; DeCoro and
+                        Tatarchuk 2007): one wave per cell sums the corner quadrics in a fixed order and solves for the representative;
+  * clean               bit-equal vertices merged, faces with a repeated index, of exactly zero area, or duplicated dropped;
+  * topology            boundary / manifold / non-manifold / misoriented edges, the Euler number: is the mesh closed and oriented?
+Bitwise reproducible; tests/simplify_ref.py restates the law in numpy.
 """
 from __future__ import annotations
 
@@ -1196,3 +1203,261 @@ def surface_scores(pred, trgt, n_samples: int, threshold: float = 0.05, draws=No
         m = sums / torch.tensor([[float(n_samples)]], dtype=torch.float64, device=dev)
         f = 2.0 * m[0, 1] * m[1, 1] / (m[0, 1] + m[1, 1])
     return {"Acc": m[0, 0], "Comp": m[1, 0], "Prec": m[0, 1], "Recal": m[1, 1], "F-score": f}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Simplification, cleaning, topology (csrc/simplify.hip, csrc/quadric.h; include/i2sdf.h, "Mesh simplification", states the law)
+class SimplifyResult(NamedTuple):
+    mesh: Mesh               # normals None when the input had none
+    vertex_map: torch.Tensor  # (V,) int32: input vertex -> output vertex, -1 when its cell is referenced by no surviving face
+    face_map: torch.Tensor   # (F_out,) int32: output face -> input face
+    fallback: torch.Tensor   # (V_out,) bool: the quadric minimiser was not used (it left the cell, or there was no quadric): the mean
+
+
+class CleanResult(NamedTuple):
+    mesh: Mesh
+    vertex_map: torch.Tensor  # (V,) int32: input vertex -> output vertex, -1 when no kept face references it
+    face_map: torch.Tensor   # (F_out,) int32: output face -> input face
+
+
+class MeshTopology:
+    """The edge statistics of a mesh (topology): `counts` is a (lib.TOPO_COUNTS,) int64 device tensor indexed by lib.TOPO; nothing is
+    read back until as_dict() (or one of the properties) asks, and then once."""
+
+    def __init__(self, counts: torch.Tensor, status: torch.Tensor):
+        self.counts, self.status = counts, status
+        self._host = None
+
+    def as_dict(self) -> dict:
+        if self._host is None:
+            c = torch.cat([self.counts, self.status.to(torch.int64)]).tolist()
+            if c[-1]:
+                raise _bad_faces("topology")
+            t = L.TOPO
+            self._host = {"edges": c[t["EDGES"]], "boundary_edges": c[t["BOUNDARY"]], "manifold_edges": c[t["MANIFOLD"]],
+                          "nonmanifold_edges": c[t["NONMANIFOLD"]], "misoriented_edges": c[t["MISORIENTED"]],
+                          "repeated_index_faces": c[t["REPEATED_FACES"]], "referenced_vertices": c[t["VERTICES"]], "faces": c[t["FACES"]],
+                          "euler": c[t["EULER"]]}
+        return dict(self._host)
+
+    @property
+    def watertight(self) -> bool:
+        """no boundary edge and no non-manifold edge (an empty mesh is watertight by this rule)"""
+        d = self.as_dict()
+        return d["boundary_edges"] == 0 and d["nonmanifold_edges"] == 0
+
+    @property
+    def oriented(self) -> bool:
+        """no 2-face edge that both faces traverse in the same direction"""
+        return self.as_dict()["misoriented_edges"] == 0
+
+    def __repr__(self):
+        return f"MeshTopology({self.as_dict()})"
+
+
+def _simplify_mesh(mesh, what):
+    """(verts, faces, normals or None) of a Mesh / (verts, faces[, normals]) on one GPU; a CPU mesh is refused by name"""
+    if not isinstance(mesh, (tuple, list)) or isinstance(mesh, MeshBVH) or len(mesh) < 2:
+        raise ValueError(f"{what}: expected a Mesh or a (verts, faces[, normals]) tuple, got {type(mesh).__name__}")
+    normals = mesh[2] if len(mesh) > 2 else None
+    for t, dt, name in ((mesh[0], torch.float32, "verts"), (mesh[1], torch.int32, "faces"), (normals, torch.float32, "normals")):
+        if t is None and name == "normals":
+            continue
+        if not torch.is_tensor(t) or t.dtype != dt or t.dim() != 2 or t.shape[1] != 3:
+            raise ValueError(f"{what}: {name} must be a (n, 3) {dt} tensor")
+        if t.device != mesh[0].device:
+            raise ValueError(f"{what}: verts on {mesh[0].device}, {name} on {t.device}")
+    if normals is not None and normals.shape[0] != mesh[0].shape[0]:
+        raise ValueError(f"{what}: {normals.shape[0]} normals for {mesh[0].shape[0]} vertices")
+    if mesh[0].shape[0] > 2 ** 31 - 1 or mesh[1].shape[0] > (2 ** 31 - 1) // 3:
+        raise ValueError(f"{what}: at most 2^31 - 1 vertices and (2^31 - 1) / 3 faces")
+    if not mesh[0].is_cuda:
+        raise L.I2SDFError(f"{what}: the mesh is on {mesh[0].device}; it runs on the GPU only, there is no CPU path")
+    return mesh[0].contiguous(), mesh[1].contiguous(), None if normals is None else normals.contiguous()
+
+
+def _sort_pairs(hi, lo):
+    """stable lexicographic sort of (hi, lo) -> (sorted hi, sorted lo, perm): two stable sorts, the minor key first"""
+    slo, p1 = torch.sort(lo, stable=True)
+    shi, p2 = torch.sort(hi[p1], stable=True)
+    return shi, slo[p2], p1[p2]
+
+
+def _keep_and_compact(src_verts, src_normals, mapped, hi, lo, duplicated, status, what, ev=lambda label: None):
+    """the kept faces of `mapped` (F, 3) over the table src_verts, compacted -> (Mesh, vflag, vscan, face_map)"""
+    lib = L.load()
+    F, n_src, dev = mapped.shape[0], src_verts.shape[0], mapped.device
+    st = L.stream_ptr()
+    if duplicated and F:
+        shi, slo, perm = _sort_pairs(hi, lo)
+        keep = torch.empty(F, dtype=torch.uint8, device=dev)
+        L.check(lib.i2sdf_simplify_run_heads(L.ptr(shi), L.ptr(slo), L.ptr(perm), F, L.ptr(keep), None, st), "i2sdf_simplify_run_heads")
+    else:
+        keep = ((hi != 2 ** 63 - 1) | (lo != 2 ** 63 - 1)).to(torch.uint8)
+    ev("faces")
+    fkeep = torch.empty(F, dtype=torch.int32, device=dev)
+    vflag = torch.empty(n_src, dtype=torch.int32, device=dev)
+    mstatus = _new_status(dev)
+    L.check(lib.i2sdf_mesh_compact_mark(L.ptr(mapped), L.ptr(keep), F, n_src, L.ptr(fkeep), L.ptr(vflag), L.ptr(mstatus), st),
+            "i2sdf_mesh_compact_mark")
+    fscan = torch.cumsum(fkeep, 0, dtype=torch.int32)
+    vscan = torch.cumsum(vflag, 0, dtype=torch.int32)
+    last = lambda t: t[-1:] if t.numel() else torch.zeros(1, dtype=torch.int32, device=dev)
+    n_f, n_v, bad, bad2 = torch.cat([last(fscan), last(vscan), status, mstatus]).tolist()      # the one host read
+    if bad or bad2:
+        raise _bad_faces(what)
+    out_v = torch.empty(n_v, 3, dtype=torch.float32, device=dev)
+    out_n = None if src_normals is None else torch.empty(n_v, 3, dtype=torch.float32, device=dev)
+    out_f = torch.empty(n_f, 3, dtype=torch.int32, device=dev)
+    L.check(lib.i2sdf_mesh_compact_gather(L.ptr(src_verts), L.ptr(src_normals), n_src, L.ptr(mapped), F, L.ptr(fkeep), L.ptr(fscan), L.ptr(vflag),
+                                          L.ptr(vscan), L.ptr(out_v), L.ptr(out_n), L.ptr(out_f), n_v, n_f, st), "i2sdf_mesh_compact_gather")
+    face_map = torch.nonzero(fkeep).reshape(-1).to(torch.int32)
+    return Mesh(out_v, out_f, out_n), vflag, vscan, face_map
+
+
+def _vertex_map(table_of_vertex, vflag, vscan):
+    """input vertex -> row of the compacted table, -1 where its table entry was not kept"""
+    if table_of_vertex.numel() == 0 or vflag.numel() == 0:
+        return torch.full_like(table_of_vertex, -1)
+    idx = table_of_vertex.to(torch.int64)
+    return torch.where(vflag[idx] != 0, vscan[idx] - 1, torch.full_like(table_of_vertex, -1)).to(torch.int32)
+
+
+@torch.no_grad()
+def simplify_vertex_clustering(mesh, voxel_size: float, contraction: str = "quadric", reg: float = 1e-3, _stats=None) -> SimplifyResult:
+    """Vertex clustering on the grid of voxel_down_sample (cell edge `voxel_size`) by the law of include/i2sdf.h ("Mesh simplification"):
+    every vertex goes to its cell; a cell's representative is, for contraction="quadric", the minimiser of the cell's summed face
+    quadrics, regularised towards the cell mean by reg * trace and replaced by the mean (fallback) when it leaves the cell -- it keeps
+    edges and corners, which the mean rounds off; for contraction="average" the mean itself, bit-equal to voxel_down_sample's row.  Faces
+    with two corners in one cell are dropped, duplicates of the same orientation merged into the smallest face index; faces stay in
+    input order, vertices come in ascending (ix, iy, iz).  Normals, when the mesh has them, are the normalised sums per cell.
+    Clustering does not preserve manifoldness: `topology` says what came out.  fp64 sums in a fixed order: bitwise reproducible.
+    A non-finite coordinate, a cell index beyond 21 bits per axis or a face index outside [0, V) raises I2SDFError.  Two host
+    synchronisations size the results (the number of cells; the numbers of kept faces and referenced cells)."""
+    what = "simplify_vertex_clustering"
+    if contraction not in L.SIMPLIFY_CONTRACTIONS:
+        raise ValueError(f"{what}: contraction = {contraction!r} is none of {sorted(L.SIMPLIFY_CONTRACTIONS)}")
+    voxel_size, reg = float(voxel_size), float(reg)
+    if not (0.0 < voxel_size < float("inf")):
+        raise ValueError(f"{what}: voxel_size = {voxel_size} must be positive and finite")
+    if not (0.0 < reg < float("inf")):
+        raise ValueError(f"{what}: reg = {reg} must be positive and finite")
+    verts, faces, normals = _simplify_mesh(mesh, what)
+    V, F, dev = verts.shape[0], faces.shape[0], verts.device
+    lib = L.load()
+    ev = _marker(_stats)
+    i32 = torch.int32
+    with torch.cuda.device(dev):
+        st = L.stream_ptr()
+        if V == 0:
+            if F:
+                raise _bad_faces(what)
+            return SimplifyResult(Mesh(verts, faces, normals), torch.empty(0, dtype=i32, device=dev), torch.empty(0, dtype=i32, device=dev),
+                                  torch.empty(0, dtype=torch.bool, device=dev))
+        pstatus = _points_status(dev)
+        status = _new_status(dev)
+        bounds = torch.empty(8, dtype=i32, device=dev)
+        keys = torch.empty(V, dtype=torch.int64, device=dev)
+        heads = torch.empty(V, dtype=i32, device=dev)
+        ev("start")
+        L.check(lib.i2sdf_points_bounds(L.ptr(verts), V, L.ptr(bounds), L.ptr(pstatus), st), "i2sdf_points_bounds")
+        L.check(lib.i2sdf_points_voxel_keys(L.ptr(verts), V, L.ptr(bounds), voxel_size, L.ptr(keys), L.ptr(pstatus), st), "i2sdf_points_voxel_keys")
+        skeys, perm = torch.sort(keys, stable=True)            # stable: a cell's vertices stay in ascending index order
+        del keys
+        L.check(lib.i2sdf_points_voxel_heads(L.ptr(skeys), V, L.ptr(heads), st), "i2sdf_points_voxel_heads")
+        scan = torch.cumsum(heads, 0, dtype=i32)
+        M, flags = torch.cat([scan[-1:], pstatus[:1]]).tolist()
+        _raise_points_status(flags, what)
+        vcell = torch.empty(V, dtype=i32, device=dev)
+        cell_start = torch.empty(M + 1, dtype=i32, device=dev)
+        L.check(lib.i2sdf_simplify_vertex_cells(L.ptr(skeys), L.ptr(perm), L.ptr(scan), V, M, L.ptr(vcell), L.ptr(cell_start), st),
+                "i2sdf_simplify_vertex_cells")
+        quadric = contraction == "quadric"
+        cperm = cruns = None
+        if quadric:
+            ckeys = torch.empty(3 * F, dtype=i32, device=dev)
+            cruns = torch.empty(M, 2, dtype=i32, device=dev)
+            L.check(lib.i2sdf_simplify_corner_keys(L.ptr(faces), F, V, L.ptr(vcell), M, L.ptr(ckeys), L.ptr(status), st), "i2sdf_simplify_corner_keys")
+            sck, cperm = torch.sort(ckeys, stable=True)       # stable: a cell's corners stay in ascending corner, hence face, order
+            L.check(lib.i2sdf_simplify_corner_runs(L.ptr(sck), F, M, L.ptr(cruns), st), "i2sdf_simplify_corner_runs")
+        ev("keys_sort")
+        cell_v = torch.empty(M, 3, dtype=torch.float32, device=dev)
+        cell_n = None if normals is None else torch.empty(M, 3, dtype=torch.float32, device=dev)
+        cell_fb = torch.empty(M, dtype=torch.uint8, device=dev)
+        L.check(lib.i2sdf_simplify_cells(L.ptr(verts), L.ptr(normals), V, L.ptr(faces), F, L.ptr(bounds), voxel_size, reg,
+                                         L.SIMPLIFY_CONTRACTIONS[contraction], L.ptr(skeys), L.ptr(perm), L.ptr(cell_start), L.ptr(cperm),
+                                         L.ptr(cruns), M, L.ptr(cell_v), L.ptr(cell_n), L.ptr(cell_fb), st), "i2sdf_simplify_cells")
+        ev("reduce_solve")
+        mapped = torch.empty(F, 3, dtype=i32, device=dev)
+        hi = torch.empty(F, dtype=torch.int64, device=dev)
+        lo = torch.empty(F, dtype=torch.int64, device=dev)
+        L.check(lib.i2sdf_simplify_face_keys(None, V, L.ptr(faces), F, L.ptr(vcell), M, L.SIMPLIFY_DROP_REPEATED, L.ptr(mapped), L.ptr(hi), L.ptr(lo),
+                                             L.ptr(status), st), "i2sdf_simplify_face_keys")
+        out, vflag, vscan, face_map = _keep_and_compact(cell_v, cell_n, mapped, hi, lo, True, status, what, ev)
+        vertex_map = _vertex_map(vcell, vflag, vscan)
+        fallback = cell_fb[vflag != 0].view(torch.bool)
+        ev("compaction")
+    return SimplifyResult(out, vertex_map, face_map, fallback)
+
+
+@torch.no_grad()
+def clean(mesh, merge_vertices: bool = True, degenerate: bool = True, zero_area: bool = True, duplicated: bool = True) -> CleanResult:
+    """A mesh without the things the consumers trip over, by the rules of include/i2sdf.h ("Mesh simplification"):
+      merge_vertices  vertices with bit-equal positions (-0.0 = +0.0) become the smallest index among them (its normal is kept);
+      degenerate      faces with a repeated index (after merging) are dropped;
+      zero_area       so are faces whose fp64 (b - a) x (c - a) is exactly zero -- the faces closest_point never reports;
+      duplicated      of the faces with the same cyclic vertex sequence the smallest index stays (opposite orientations both stay);
+    then vertices that no kept face references are dropped.  Faces and vertices keep their relative order.  Nothing is moved, so the
+    result is exact.  One host synchronisation sizes the result; a face index outside [0, V) raises I2SDFError."""
+    what = "clean"
+    verts, faces, normals = _simplify_mesh(mesh, what)
+    V, F, dev = verts.shape[0], faces.shape[0], verts.device
+    lib = L.load()
+    i32 = torch.int32
+    with torch.cuda.device(dev):
+        st = L.stream_ptr()
+        status = _new_status(dev)
+        vmap = torch.arange(V, dtype=i32, device=dev)
+        if merge_vertices and V:
+            khi = torch.empty(V, dtype=torch.int64, device=dev)
+            klo = torch.empty(V, dtype=torch.int64, device=dev)
+            L.check(lib.i2sdf_simplify_position_keys(L.ptr(verts), V, L.ptr(khi), L.ptr(klo), st), "i2sdf_simplify_position_keys")
+            shi, slo, perm = _sort_pairs(khi, klo)              # stable: the first of a run is its smallest index
+            first = torch.empty(V, dtype=i32, device=dev)
+            L.check(lib.i2sdf_simplify_run_heads(L.ptr(shi), L.ptr(slo), L.ptr(perm), V, None, L.ptr(first), st), "i2sdf_simplify_run_heads")
+            head = torch.cummax(first, 0).values.to(torch.int64)
+            vmap[perm] = perm[head].to(i32)
+        flags = (L.SIMPLIFY_DROP_REPEATED if degenerate else 0) | (L.SIMPLIFY_DROP_ZERO_AREA if zero_area else 0)
+        mapped = torch.empty(F, 3, dtype=i32, device=dev)
+        hi = torch.empty(F, dtype=torch.int64, device=dev)
+        lo = torch.empty(F, dtype=torch.int64, device=dev)
+        L.check(lib.i2sdf_simplify_face_keys(L.ptr(verts), V, L.ptr(faces), F, L.ptr(vmap), V, flags, L.ptr(mapped), L.ptr(hi), L.ptr(lo),
+                                             L.ptr(status), st), "i2sdf_simplify_face_keys")
+        out, vflag, vscan, face_map = _keep_and_compact(verts, normals, mapped, hi, lo, bool(duplicated), status, what)
+        vertex_map = _vertex_map(vmap, vflag, vscan)
+    return CleanResult(out, vertex_map, face_map)
+
+
+@torch.no_grad()
+def topology(mesh) -> MeshTopology:
+    """What kind of mesh this is, from its edges (include/i2sdf.h, "Mesh simplification", edge statistics): unique undirected edges;
+    boundary (1 face), manifold (2 faces) and non-manifold (3 or more) edges; misoriented edges (a 2-face edge both faces traverse in
+    the same direction); faces with a repeated index (their edges are left out); the vertices the other faces reference and the Euler
+    number V_ref - E + F over them.  `.watertight` (no boundary, no non-manifold edge) and `.oriented` (no misoriented edge) are what
+    signed_distance(sign="pseudonormal") needs; choose sign="winding" otherwise.  Enqueues only: the counts stay on the device until
+    as_dict() reads them once."""
+    what = "topology"
+    verts, faces, _ = _simplify_mesh(mesh[:2] if isinstance(mesh, (tuple, list)) and not isinstance(mesh, MeshBVH) else mesh, what)
+    V, F, dev = verts.shape[0], faces.shape[0], verts.device
+    lib = L.load()
+    with torch.cuda.device(dev):
+        st = L.stream_ptr()
+        status = _new_status(dev)
+        counts = torch.empty(L.TOPO_COUNTS, dtype=torch.int64, device=dev)
+        keys = torch.empty(3 * F, dtype=torch.int64, device=dev)
+        vflag = torch.empty(V, dtype=torch.int32, device=dev)
+        L.check(lib.i2sdf_mesh_edge_stats_keys(L.ptr(faces), F, V, L.ptr(keys), L.ptr(vflag), L.ptr(counts), L.ptr(status), st),
+                "i2sdf_mesh_edge_stats_keys")
+        skeys = torch.sort(keys)[0]                             # (the order inside a run of equal keys does not change a count)
+        L.check(lib.i2sdf_mesh_edge_stats(L.ptr(skeys), F, L.ptr(counts), st), "i2sdf_mesh_edge_stats")
+    return MeshTopology(counts, status)

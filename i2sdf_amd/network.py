@@ -917,12 +917,19 @@ class I2SDFNetwork(nn.Module):
         return out
 
     @torch.no_grad()
-    def extract_mesh(self, axes, level: float = 0.0, rot=None, trans=None, chunk: int = 1 << 21, device=None):
+    def extract_mesh(self, axes, level: float = 0.0, rot=None, trans=None, chunk: int = 1 << 21, device=None, simplify=None,
+                     contraction: str = "quadric"):
         """The `level` set of the SDF on a grid as a device mesh (i2sdf_amd.mesh.Mesh: verts, faces, normals): sdf_volume(axes,
         rot, trans) followed by i2sdf_amd.mesh.marching_cubes, with the reference's spacing (the x step for all three axes,
         GridAxes.spacing) and its grid origin added (model/eval/recon.py:53-60).  Vertices and normals are returned in world
         space: rot @ (v + origin) + trans and rot @ n, which on the PCA-aligned grid (rot = vecs^T, trans = s_mean) equals
-        the reference's vecs^T @ verts + grid_points[0] (:93-95).  Empty tensors when nothing crosses the level."""
+        the reference's vecs^T @ verts + grid_points[0] (:93-95).  Empty tensors when nothing crosses the level.
+        simplify: a cell size -> the mesh goes through i2sdf_amd.mesh.clean and simplify_vertex_clustering(mesh, simplify,
+        contraction) before it is returned (in world space); None, the default, is the path above, untouched."""
+        if simplify is not None:
+            from .mesh import clean, simplify_vertex_clustering
+            m = self.extract_mesh(axes, level, rot, trans, chunk, device)
+            return simplify_vertex_clustering(clean(m).mesh, simplify, contraction).mesh
         from .mesh import Mesh, marching_cubes
         x, y, z = (axes.x, axes.y, axes.z) if hasattr(axes, "shortest_axis_index") else axes
         x = torch.as_tensor(x, dtype=torch.float64)

@@ -1526,6 +1526,116 @@ int i2sdf_winding_bvh(const void* bvh, const void* moments, int64_t F, const flo
 int i2sdf_winding_brute(const float* verts, int64_t V, const int32_t* faces, int64_t F, const float* points, int64_t n, double* w_out,
                         int32_t* status, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Mesh simplification -- vertex clustering with quadric placement (Lindstrom, Out-of-core simplification of large polygonal models,
+ * SIGGRAPH 2000; DeCoro and Tatarchuk, Real-time mesh simplification using the GPU, I3D 2007), mesh cleaning, and the edge statistics
+ * of a topology report: the step between the mesh producers (marching cubes, TSDF fusion) and the consumers (the tree, closest point,
+ * winding number, the scores).  The decimation that needs no priority queue and whose result is an order-free function of its input.
+ * csrc/simplify.hip, csrc/quadric.h.  No plan.  Every call only enqueues on `stream`: no allocation, no synchronisation, no host
+ * read; the caller sorts (stable) and scans between the calls and reads the counts that size the results.  tests/simplify_ref.py
+ * restates the law in numpy.
+ *
+ * The law.  verts (V, 3) fp32, faces (F, 3) int32, normals (V, 3) fp32 or none; cell edge h, finite and positive; reg, finite and
+ * positive (1e-3: Lindstrom's truncation level).
+ *   Arithmetic.  fp64 on the exact images of the fp32 inputs; every operation is ONE IEEE operation, rounded to nearest, in the order
+ *         written, none contracted into an FMA; a dot product x.y is (x0 y0 + x1 y1) + x2 y2.
+ *   Grid.  Exactly that of "Point sets" (voxel_down_sample): lo = min(verts) - h / 2 per axis over ALL vertices, referenced by a face or
+ *         not; cell index = floor((p - lo) / h), 21 bits per axis, key = ix << 42 | iy << 21 | iz; a non-finite coordinate or an index
+ *         beyond 21 bits is refused through the status word of i2sdf_points_voxel_keys.  Cells are numbered in ascending key order, i.e.
+ *         ascending (ix, iy, iz).  Cell centre cc_k = lo_k + (i_k + 0.5) h.
+ *   Face quadric about a centre cc.  For face (a, b, c):  n = (b - a) x (c - a) = (e1 g2 - e2 g1, e2 g0 - e0 g2, e0 g1 - e1 g0) with
+ *         e = b - a, g = c - a (not normalised: a face weighs in by its squared area);  d = -(n . (a - cc)), taken about the centre of
+ *         the cell it is added to, so that a mesh at +1000 does not cancel;  nine values: n0 n0, n0 n1, n0 n2, n1 n1, n1 n2, n2 n2 (A)
+ *         and d n0, d n1, d n2 (bvec).
+ *   Corners.  The quadric of face f is added once per corner to the cell of that corner (a face inside one cell adds three times:
+ *         measured better than once per distinct cell, 6.3e-3 against 7.7e-3 of the radius on the icosphere at h = 0.25).  A face with
+ *         an index outside [0, V) is never dereferenced: it sets I2SDF_SIMPLIFY_BAD_FACE and adds nothing.
+ *   Sums.  The 3 F corners are grouped by a stable sort of their cell id, so a cell's run is in ascending corner index 3 f + k.  The
+ *         corner at position j of its run (j = 0, 1, ...) belongs to lane j mod 64; a lane adds its corners in ascending j into nine
+ *         partials that start at +0; the 64 partials p[0..63] of a value are combined by the xor butterfly: for s = 32, 16, 8, 4, 2, 1:
+ *         p[l] <- p[l] + p[l xor s] for all l at once; the sum is p[0].  No floating-point atomics: the order does not depend on arrival.
+ *   Cell mean.  m = (the sum of the cell's vertices in ascending index, from +0) / count - cc, per axis.
+ *   Representative, I2SDF_SIMPLIFY_QUADRIC.  tr = (A00 + A11) + A22;  lambda = reg tr;  M = A + lambda I;  r = lambda m - bvec;
+ *         cofactors c00 = M11 M22 - M12 M12, c01 = M02 M12 - M01 M22, c02 = M01 M12 - M02 M11, c11 = M00 M22 - M02 M02,
+ *         c12 = M01 M02 - M00 M12, c22 = M00 M11 - M01 M01;  det = M0 . (c00, c01, c02);  x_i = ((c_i0, c_i1, c_i2) . r) / det.
+ *         If tr is not finite and positive, or |x_i| <= h / 2 fails for some i (the minimiser left its cell, or is not a number):
+ *         x = m and the cell's fallback flag is set.  Output vertex = fp32(cc + x).
+ *   Representative, I2SDF_SIMPLIFY_AVERAGE.  fp32(sum / count): bit-equal to the matching row of i2sdf_points_voxel_mean.  No flag.
+ *   Normals (when given).  s = the sum of the cell's input normals in ascending vertex index; len = sqrt(s . s); fp32(s / len), zeros
+ *         when len is not finite and positive.
+ *   Faces.  Corners are replaced by cell ids.  A face with two corners in one cell is dropped.  Two surviving faces with the same
+ *         cyclic sequence of cells (the same orientation) are duplicates: the smallest input face index is kept; opposite orientations
+ *         are both kept.  The key of a face is the lexicographically smallest rotation (t0, t1, t2) of its triple: key_hi = t0,
+ *         key_lo = t1 << 32 | t2; two stable sorts (by key_lo, then by key_hi) bring equal keys together in ascending face order.
+ *         Output faces come in ascending input face index with the corner order of the input; output vertices are the cells a
+ *         surviving face references, in ascending (ix, iy, iz) (i2sdf_mesh_compact_mark / _gather over the cell table).
+ *   Cleaning uses the same face kernel with another vertex map: vertices with bit-equal positions (-0.0 = +0.0) merged into the smallest
+ *         index among them; I2SDF_SIMPLIFY_DROP_REPEATED drops a face with a repeated (mapped) index, I2SDF_SIMPLIFY_DROP_ZERO_AREA one
+ *         whose n above is exactly (0, 0, 0) -- "Closest point"'s never-closest rule.  Without DROP_REPEATED the key is still one per
+ *         cyclic sequence.
+ *   F = 0, 1, 2 and V = 0 are legal.
+ *
+ * i2sdf_simplify_vertex_cells: from the sorted vertex keys, the permutation and the inclusive scan of i2sdf_points_voxel_heads:
+ *   vertex_cell (V) = the cell of every vertex, cell_start (n_cells + 1) = where every cell's run begins in the sorted order (the last
+ *   entry is V).
+ * i2sdf_simplify_corner_keys: corner_keys (3 F) int32 = the cell of every corner; n_cells for the corners of a refused face.
+ * i2sdf_simplify_corner_runs: corner_runs (n_cells, 2) int32 = begin and end of every cell's corners in the sorted corner order
+ *   (0, 0 for a cell no face touches).
+ * i2sdf_simplify_cells: the hot kernel, one wave per cell: out_verts (n_cells, 3), out_normals (n_cells, 3; untouched when normals is
+ *   NULL), fallback (n_cells) uint8.  bounds: what i2sdf_points_bounds wrote.  With I2SDF_SIMPLIFY_AVERAGE faces, corner_perm and
+ *   corner_runs are not read.
+ * i2sdf_simplify_face_keys: out_faces (F, 3) = the mapped corners (vertex_map NULL: the identity; -1 for a refused face), the key pair
+ *   (INT64_MAX twice for a face that is not kept).  A face with an index outside [0, V), or mapped outside [0, n_map), sets
+ *   I2SDF_SIMPLIFY_BAD_FACE and is not kept.
+ * i2sdf_simplify_run_heads: keep[perm[i]] = 1 where sorted entry i is the first of its run of equal key pairs and not INT64_MAX twice,
+ *   else 0; first[i] = i at the first of a run, else 0 (its running maximum is the head of every entry's run).  Either may be NULL.
+ * i2sdf_simplify_position_keys: key_hi = the bits of x, key_lo = the bits of y << 32 | the bits of z, -0.0 as +0.0.
+ *
+ * Edge statistics (the topology report).  Faces with an index outside [0, V) set I2SDF_SIMPLIFY_BAD_FACE and are left out; faces with
+ *   a repeated index are counted and their edges left out.  Of the others: every side is an undirected edge (min, max) with a
+ *   direction bit; after the caller's sort, an edge with 1 face is a boundary edge, with 2 faces a manifold edge, with 3 or more a
+ *   non-manifold edge; a 2-face edge traversed in the same direction by both is misoriented.  counts (I2SDF_TOPO_COUNTS) int64, integer
+ *   atomics only.  Euler = VERTICES - EDGES + FACES, over the counted faces and the vertices they reference.
+ * i2sdf_mesh_edge_stats_keys: clears counts and vflag (V) int32, writes keys (3 F; INT64_MAX for a side left out), marks and counts
+ *   the referenced vertices, counts the faces.  i2sdf_mesh_edge_stats: the edge counts from the sorted keys, then the Euler number.
+ *
+ * Refused with I2SDF_EINVAL before any launch: a NULL or misaligned pointer (stream excepted; pointers of empty arrays too), V or
+ *   n_cells outside 0..2^31-1, F outside 0..(2^31-1)/3, n_cells > V, a voxel_size or reg that is not finite and positive, an unknown
+ *   contraction or flag.
+ * ---------------------------------------------------------------------------------------------- */
+#define I2SDF_SIMPLIFY_QUADRIC 0
+#define I2SDF_SIMPLIFY_AVERAGE 1
+#define I2SDF_SIMPLIFY_BAD_FACE 1          /* status bit 0 */
+#define I2SDF_SIMPLIFY_DROP_REPEATED 1     /* flags of i2sdf_simplify_face_keys */
+#define I2SDF_SIMPLIFY_DROP_ZERO_AREA 2
+#define I2SDF_TOPO_EDGES 0                 /* indices into counts */
+#define I2SDF_TOPO_BOUNDARY 1
+#define I2SDF_TOPO_MANIFOLD 2
+#define I2SDF_TOPO_NONMANIFOLD 3
+#define I2SDF_TOPO_MISORIENTED 4
+#define I2SDF_TOPO_REPEATED_FACES 5
+#define I2SDF_TOPO_VERTICES 6
+#define I2SDF_TOPO_EULER 7
+#define I2SDF_TOPO_FACES 8
+#define I2SDF_TOPO_COUNTS 10               /* (entry 9 is reserved and 0) */
+int i2sdf_simplify_vertex_cells(const int64_t* sorted_keys, const int64_t* perm, const int32_t* head_scan, int64_t V, int64_t n_cells,
+                                int32_t* vertex_cell, int32_t* cell_start, void* stream);
+int i2sdf_simplify_corner_keys(const int32_t* faces, int64_t F, int64_t V, const int32_t* vertex_cell, int64_t n_cells, int32_t* corner_keys,
+                               int32_t* status, void* stream);
+int i2sdf_simplify_corner_runs(const int32_t* sorted_corner_keys, int64_t F, int64_t n_cells, int32_t* corner_runs, void* stream);
+int i2sdf_simplify_cells(const float* verts, const float* normals, int64_t V, const int32_t* faces, int64_t F, const int32_t* bounds,
+                         double voxel_size, double reg, int32_t contraction, const int64_t* sorted_keys, const int64_t* perm,
+                         const int32_t* cell_start, const int64_t* corner_perm, const int32_t* corner_runs, int64_t n_cells, float* out_verts,
+                         float* out_normals, uint8_t* fallback, void* stream);
+int i2sdf_simplify_face_keys(const float* verts, int64_t V, const int32_t* faces, int64_t F, const int32_t* vertex_map, int64_t n_map,
+                             int32_t flags, int32_t* out_faces, int64_t* key_hi, int64_t* key_lo, int32_t* status, void* stream);
+int i2sdf_simplify_run_heads(const int64_t* sorted_hi, const int64_t* sorted_lo, const int64_t* perm, int64_t n, uint8_t* keep,
+                             int32_t* first, void* stream);
+int i2sdf_simplify_position_keys(const float* verts, int64_t V, int64_t* key_hi, int64_t* key_lo, void* stream);
+int i2sdf_mesh_edge_stats_keys(const int32_t* faces, int64_t F, int64_t V, int64_t* keys, int32_t* vflag, int64_t* counts, int32_t* status,
+                               void* stream);
+int i2sdf_mesh_edge_stats(const int64_t* sorted_keys, int64_t F, int64_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
